@@ -1,7 +1,8 @@
 """bench.py — images/s of the RetinaNet hot path on MI355X (BASELINE.json metric:
 "images/sec train+infer, ResNet50-640 RetinaNet, 1/2/4/8 MI355X").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N>1: launched by torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                                  (N>1: launched by torch.distributed.run)
 
 `value` = data-parallel TRAINING throughput (the path that shards): every rank runs the per-GPU
 shard of BASELINE configs[2] — ResNet50-640x640 bf16, 32 images per GPU (global batch 256 at
@@ -9,9 +10,14 @@ N=8), `resnet_initial` frozen, SyncBN when N>1 — and one step is
   targets encoded on the GPU (a2-a4) -> forward with training-mode BatchNorm -> focal + Huber
   loss forward/backward -> backward through heads / FPN / ResNet -> weight decay, per-tensor and
   global clipping -> RCCL all-reduce of the gradient arena -> SGD momentum + EMA.
-Weak scaling: per-GPU work is fixed, value = N * 32 * K / max-over-ranks time.
+Weak scaling: per-GPU work is fixed, value = N * 32 * K / max-over-ranks time; `ms_per_step` = time of one timed step.
 
-At N=1 the line also carries `infer`: BASELINE configs[1] (bf16 inference, batch 8, images
+A plain run does only that: set up, W warm-up steps, K timed steps, the JSON line.  `--dump-outputs DIR` then
+writes what the last timed step computed (step_outputs) as DIR/<name>.npy.  Everything below is measured only
+with `--full` (the `--no-*` switches leave parts of it out); the HIP events of the roofline attribution then
+bracket the conv launches of every 5th timed step.
+
+With --full, at N=1 the line also carries `infer`: BASELINE configs[1] (bf16 inference, batch 8, images
 resident in HBM -> backbone + FPN + heads -> decode + per-class top-k + NMS -> detections),
 which does not shard ("replicas only"), and `cpu_baseline`: the CPU restatement
 (oracle/model_ref.py, PyTorch-CPU — NOT TensorFlow) timed on the host cores.
@@ -115,6 +121,37 @@ def synth_ground_truth(B, size, seed):
     return torch.from_numpy(gb), torch.from_numpy(gc), torch.from_numpy(cnt)
 
 
+DUMP_SAMPLE = 1 << 22          # elements of each weight arena in --dump-outputs (16 MB as float32)
+DUMP_LIMIT = 64 << 20          # bytes of all --dump-outputs files together
+
+
+def step_outputs(out, eng, seed=1337):
+    """What one training step hands its caller, as host float32 arrays by file name: the loss dict of
+    TrainEngine.train_step (scalars), and what the step updated — the fp32 weight arena after SGD and, when the optimizer
+    keeps one, its EMA shadow — as a fixed seeded sample of DUMP_SAMPLE positions (the same for every run of a model)."""
+    res = {}
+    for k, v in out.items():
+        a = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float32)
+        res[k.replace("-", "_")] = a.astype(np.float32)
+    n = eng.P.numel()
+    idx = np.sort(np.random.default_rng(seed).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    idx = torch.from_numpy(idx).to(eng.P.device)
+    res["weights_sample"] = eng.P[idx].float().cpu().numpy()
+    if getattr(eng.model.optimizer, "use_moving_average", False):
+        res["ema_weights_sample"] = eng.E[idx].float().cpu().numpy()
+    return res
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy per array of step_outputs, DUMP_LIMIT bytes at most in all"""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------
 def run_train(args, dev, rank, world, params=None):
     """params: another configuration than BASELINE configs[2] (the `extra` entries of the N = 1 line)"""
@@ -152,7 +189,7 @@ def run_train(args, dev, rank, world, params=None):
     sampled = 0
     t0 = time.perf_counter()
     for i in range(args.steps):
-        sample = (i % 5 == 4) or i == args.steps - 1
+        sample = args.full and ((i % 5 == 4) or i == args.steps - 1)
         eng.conv_profile = prof if sample else None
         eng.hbm_profile = hbm if sample else None
         eng.wgrad_profile = wprof if sample else None
@@ -169,6 +206,12 @@ def run_train(args, dev, rank, world, params=None):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    # the last timed step's results, read before anything else runs on this engine
+    res = {"dt": dt, "B": B, "loss": float(out["weighted-loss"].item()),
+           "grad_norm": float(out["gradient-norm"].item()),
+           "outputs": step_outputs(out, eng) if args.dump_outputs and rank == 0 else None}
+    if not args.full:
+        return res, params, model, eng
     # per kernel: [ms, flops, bytes, launches]; the dominant kernel is the one with most time.  The third template flag
     # of the 256-row kernels (BN_BWD: the epilogue also writes stage 1 of a BatchNorm backward reduction) does not make
     # another kernel — same K loop, same tiles — so its two device symbols are ONE roofline entry, with the
@@ -301,31 +344,29 @@ def run_train(args, dev, rank, world, params=None):
                          "avg_launch_us": round(ms1 * 1e3 / max(n1, 1), 2), "launches": n1, "symbols": excl_symbols,
                          "how": "one extra untimed step with RNET_WGRAD_STREAM=0 semantics (one-stream backward): "
                                 "the same launches with the chip to themselves"}
-    res = {"dt": dt, "B": B, "loss": float(out["weighted-loss"].item()),
-           "grad_norm": float(out["gradient-norm"].item()),
-           "roofline": {"bound": "mfma", "achieved": round(dom_flops / (dom_ms * 1e-3) / 1e12, 2) if dom_ms else 0.0,
-                        "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                        "frac": round(dom_flops / (dom_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) if dom_ms else 0.0,
-                        "traffic": None, "kernel": dom_name + " (forward + dgrad launches)",
-                        "launches_per_step": dom_n // max(sampled, 1), "sampled_steps": sampled,
-                        "avg_launch_us": round(dom_ms * 1e3 / max(dom_n, 1), 2),
-                        "symbols": {k: {"launches_per_step": v[3] // max(sampled, 1),
-                                        "avg_launch_us": round(v[0] * 1e3 / max(v[3], 1), 2),
-                                        "algorithmic_gflop_per_launch": round(v[1] / max(v[3], 1) / 1e9, 3)}
-                                    for k, v in by_symbol.items() if family(k) == dom_name},
-                        "ms_per_step": round(dom_ms / max(sampled, 1), 3),
-                        "algorithmic_gflop_per_launch": round(dom_flops / max(dom_n, 1) / 1e9, 3),
-                        "algorithmic_bytes_per_launch": int(dom_bytes / max(dom_n, 1)),
-                        "concurrency": ("dgrad launches overlap wgrad launches of a second stream in the timed steps"
-                                        if getattr(eng, "side_stream_on", False) else "one stream"),
-                        "exclusive": exclusive,
-                        "wgrad": wgrad_roof,
-                        "layers": layer_table(lprof, lprof1),
-                        "hbm_kernels": {"bound": "hbm", "peak": PEAK_HBM_GBS, "unit": "GB/s", "kernels": hbm_kernels,
-                                        "stream_reference": stream_reference(dev)},
-                        "other_conv_kernels": {k: {"ms_per_step": round(v[0] / max(sampled, 1), 3),
-                                                   "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1) if v[0] else 0.0}
-                                               for k, v in by_kernel.items() if k != dom_name}}}
+    res["roofline"] = {"bound": "mfma", "achieved": round(dom_flops / (dom_ms * 1e-3) / 1e12, 2) if dom_ms else 0.0,
+                      "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                      "frac": round(dom_flops / (dom_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) if dom_ms else 0.0,
+                      "traffic": None, "kernel": dom_name + " (forward + dgrad launches)",
+                      "launches_per_step": dom_n // max(sampled, 1), "sampled_steps": sampled,
+                      "avg_launch_us": round(dom_ms * 1e3 / max(dom_n, 1), 2),
+                      "symbols": {k: {"launches_per_step": v[3] // max(sampled, 1),
+                                      "avg_launch_us": round(v[0] * 1e3 / max(v[3], 1), 2),
+                                      "algorithmic_gflop_per_launch": round(v[1] / max(v[3], 1) / 1e9, 3)}
+                                  for k, v in by_symbol.items() if family(k) == dom_name},
+                      "ms_per_step": round(dom_ms / max(sampled, 1), 3),
+                      "algorithmic_gflop_per_launch": round(dom_flops / max(dom_n, 1) / 1e9, 3),
+                      "algorithmic_bytes_per_launch": int(dom_bytes / max(dom_n, 1)),
+                      "concurrency": ("dgrad launches overlap wgrad launches of a second stream in the timed steps"
+                                      if getattr(eng, "side_stream_on", False) else "one stream"),
+                      "exclusive": exclusive,
+                      "wgrad": wgrad_roof,
+                      "layers": layer_table(lprof, lprof1),
+                      "hbm_kernels": {"bound": "hbm", "peak": PEAK_HBM_GBS, "unit": "GB/s", "kernels": hbm_kernels,
+                                      "stream_reference": stream_reference(dev)},
+                      "other_conv_kernels": {k: {"ms_per_step": round(v[0] / max(sampled, 1), 3),
+                                                 "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1) if v[0] else 0.0}
+                                             for k, v in by_kernel.items() if k != dom_name}}
     return res, params, model, eng
 
 
@@ -638,6 +679,7 @@ def run_extras(args, dev):
     extra = {}
     a3 = copy.copy(args)
     a3.size, a3.train_batch, a3.steps, a3.warmup, a3.no_exclusive = 1024, 16, 5, 2, True
+    a3.dump_outputs = None
     r3, _, _, eng = run_train(a3, dev, 0, 1, default_params(input_size=1024, batch_train=16))
     rl = r3["roofline"]
     extra["config3"] = {"workload": "ResNet50-1024x1024 bf16 training, 16 images on one GPU (BASELINE configs[3] shard), "
@@ -652,6 +694,7 @@ def run_extras(args, dev):
     p4.architecture.batch_norm.use_sync = False
     a4 = copy.copy(args)
     a4.size, a4.train_batch, a4.steps, a4.warmup, a4.no_exclusive = 640, 32, 5, 2, True
+    a4.dump_outputs = None
     r4, _, _, eng = run_train(a4, dev, 0, 1, p4)
     hb = r4["roofline"]["hbm_kernels"]["kernels"]
     conv = dict(r4["roofline"].get("other_conv_kernels", {}))
@@ -837,7 +880,15 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip `extra`: BASELINE configs[3] / [4] on one GPU")
     ap.add_argument("--no-probe", action="store_true", help="skip the MFMA-only probe behind roofline.sustained")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline attribution, MFMA probe, inference "
+                         "legs, BASELINE configs[3] / [4], data-parallel overhead, CPU baseline (the --no-* switches "
+                         "leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` typed by hand: this process becomes the LAUNCHER (distribute.py:16-18: one replica
@@ -873,6 +924,8 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
     train, p_train, m_train, eng = run_train(args, dev, rank, world)
+    if train["outputs"] is not None:
+        write_outputs(args.dump_outputs, train["outputs"])
     B = train["B"]
     line = {
         "metric": "images/sec train, ResNet50-640 RetinaNet data-parallel step (encode + fwd + loss + bwd + clip + "
@@ -896,9 +949,10 @@ def main():
                    "comm": "native" if getattr(eng, "native_comm", None) is not None else "torch",
                    "syncbn_messages": getattr(eng, "syncbn_messages_per_step", None),
                    "final_loss": round(train["loss"], 4), "gradient_norm": round(train["grad_norm"], 4)},
-        "roofline": train["roofline"],
     }
-    if rank == 0 and not args.no_probe:
+    if args.full:
+        line["roofline"] = train["roofline"]
+    if args.full and rank == 0 and not args.no_probe:
         try:
             sus = mfma_sustained(dev)
             rl = line["roofline"]
@@ -912,7 +966,7 @@ def main():
         except Exception as e:   # noqa: BLE001 — a probe failure must not lose the bench line
             line["roofline"]["sustained"] = {"error": str(e)}
     tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
+    if args.full and os.path.exists(tpath):
         try:
             # profiles/traffic.json (tools/summarize_profiles.py): per device symbol, HBM bytes per launch from the
             # FETCH_SIZE / WRITE_SIZE passes of the same bench command
@@ -926,7 +980,7 @@ def main():
             line["roofline"]["traffic"] = int(tot / n) if n else None
         except Exception:
             pass
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         frozen = set(eng.frozen)
         del eng
         torch.cuda.empty_cache()

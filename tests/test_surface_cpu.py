@@ -1,6 +1,6 @@
 """CPU: the §8(b) Python surface that needs no GPU — command-line flags, config -> graph through the sub-builders,
-every shipped reference config (when /root/reference is mounted), executor helpers, input-pipeline sharding for the
-one-process-per-GPU layout, and the ctypes structs against the C header's own layout."""
+every shipped reference config (stored under tests/golden/reference_configs), executor helpers, input-pipeline
+sharding for the one-process-per-GPU layout, and the ctypes structs against the C header's own layout."""
 import copy
 import glob
 import os
@@ -12,7 +12,7 @@ import pytest
 
 from conftest import ROOT
 
-REF_CONFIGS = "/root/reference/configs"
+REF_CONFIGS = os.path.join(ROOT, "tests", "golden", "reference_configs")
 
 
 def test_flags_parse_like_absl():
@@ -80,7 +80,6 @@ def test_sub_builders_compose_the_reference_model(params):
     assert get_normalization_op(use_sync=True, num_replicas=8)["kind"] == "sync_batch_normalization"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason="reference mount absent (GPU box)")
 def test_every_shipped_config_loads_and_builds_or_says_why():
     from retinanet.cfg import Config
     from retinanet.model.graph import build_retinanet_graph

@@ -4,6 +4,6 @@
 OUT=${1:-gpurun_out/abenv}; SW=$2; shift 2
 mkdir -p $OUT
 for i in 1 2; do
-  env $SW python bench.py --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_base_$i.json 2>/dev/null
-  python bench.py --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_new_$i.json 2>/dev/null
+  env $SW python bench.py --full --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_base_$i.json 2>/dev/null
+  python bench.py --full --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_new_$i.json 2>/dev/null
 done

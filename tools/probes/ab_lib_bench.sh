@@ -4,6 +4,6 @@
 OUT=${1:-gpurun_out/ablib}; P=$(realpath $2); shift 2
 mkdir -p $OUT
 for i in 1 2; do
-  RNET_HIP_LIB=$P python bench.py --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_other_$i.json 2>/dev/null
-  python bench.py --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_new_$i.json 2>/dev/null
+  RNET_HIP_LIB=$P python bench.py --full --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_other_$i.json 2>/dev/null
+  python bench.py --full --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_new_$i.json 2>/dev/null
 done

@@ -5,6 +5,6 @@ OUT=${1:-gpurun_out/r04ab}; shift
 mkdir -p $OUT
 P=$PWD/tools/probes/bin/librnet_base.so
 for i in 1 2; do
-  RNET_HIP_LIB=$P python bench.py --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_base_$i.json 2>/dev/null
-  python bench.py --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_new_$i.json 2>/dev/null
+  RNET_HIP_LIB=$P python bench.py --full --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_base_$i.json 2>/dev/null
+  python bench.py --full --no-cpu-baseline --no-probe --no-extras "$@" > $OUT/bench_new_$i.json 2>/dev/null
 done

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/copies
 mkdir -p $OUT
 cd $R
-timeout 600 rocprofv3 --hip-trace --memory-copy-trace --kernel-trace --output-format csv -d $OUT -- python3 bench.py --steps 3 --warmup 2 --no-exclusive --no-infer --no-cpu-baseline > $OUT/run.log 2>&1
+timeout 600 rocprofv3 --hip-trace --memory-copy-trace --kernel-trace --output-format csv -d $OUT -- python3 bench.py --full --steps 3 --warmup 2 --no-exclusive --no-infer --no-cpu-baseline > $OUT/run.log 2>&1
 python3 - <<'PY'
 import csv, glob, collections, os
 out = os.environ.get("GRAFT_REPO_ROOT", ".") + "/gpurun_out/copies"
