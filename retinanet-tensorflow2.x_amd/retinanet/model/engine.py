@@ -120,6 +120,8 @@ class InferenceEngine:
             launch_opts = _C.LaunchOpts(**launch_opts)
         self.launch_opts = launch_opts.copy() if launch_opts is not None else _C.LaunchOpts()
         self._keep = []     # ctypes structs / arrays that must outlive the launches
+        self.dw_launches = []   # (name, rn_dw_problem) of every depthwise launch
+        self.se_launches = []   # (name, N, HW, C, se) of every rn_squeeze_excite_inplace launch
         self.steps = []     # list of (callable, name)
         self.t = {}         # tensor name -> torch tensor
         self.packed = {}    # conv name -> packed bf16 weight
@@ -438,6 +440,7 @@ class InferenceEngine:
         lib = self.lib
         pref = ctypes.byref(p)
         name = first.get("group") or first["out"]
+        self.dw_launches.append(("dwconv:" + name, p))
 
         def run(st):
             _C.check(lib.rn_depthwise_conv2d_nhwc_fwd(pref, st), f"rn_depthwise_conv2d_nhwc_fwd[{name}]")
@@ -520,6 +523,7 @@ class InferenceEngine:
                 args = (x.data_ptr(), B, x.shape[1] * x.shape[2], se["C"], self.packed[name + ":w1"].data_ptr(),
                         self.packed[name + ":b1"].data_ptr(), self.packed[name + ":w2"].data_ptr(),
                         self.packed[name + ":b2"].data_ptr(), se["se"], self.se_ws.data_ptr(), self.se_ws.numel())
+                self.se_launches.append(("se:" + op["tensor"], B, x.shape[1] * x.shape[2], se["C"], se["se"]))
 
                 def se_run(st, args=args, name=name):
                     _C.check(lib.rn_squeeze_excite_inplace(*args, st), f"rn_squeeze_excite_inplace[{name}]")

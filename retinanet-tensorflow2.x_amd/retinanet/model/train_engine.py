@@ -122,6 +122,10 @@ class TrainEngine:
         self.hbm_profile = None   # bench.py: list that collects (event0, event1, kernel name, algorithmic bytes)
         self.conv_launches = []   # (name, rn_conv_problem) of every implicit-GEMM launch: lib.rn_conv_kernel_id(byref(p))
         self.wgrad_launches = []  # (name, rn_wgrad_problem) of every weight-gradient launch
+        # (name, "fwd" | "dgrad", rn_dw_problem, rn_upsample_zero2x arguments run before it) of every depthwise launch
+        self.dw_launches = []
+        self.dw_wgrad_launches = []   # (name, rn_dw_problem) of every depthwise weight-gradient launch
+        self.se_launches = []     # (name, "fwd" | "bwd", N, HW, C, se) of every squeeze-excite launch
         cus = os.environ.get("RNET_WGRAD_CUS", "160,208")   # round 6, same-box A/B (profiles/r06_ab/wgrad_cus.txt): 176,256 28.23, 160,208 28.01, 144,192 28.02, 112,192 30.3 ms
         self._wgrad_cap = tuple(int(v) for v in cus.split(",")) if cus not in ("0", "") else None
         if os.environ.get("RNET_WGRAD_STREAM", "1") == "0":
@@ -1009,6 +1013,7 @@ class TrainEngine:
                     ops = [op]
                 live_bn = bool(self._bn_trainable(ops[0]))
                 pd = self._dw_problem(ops, (lambda o: self.raw[o["out"]]) if live_bn else (lambda o: self.t[o["out"]]))
+                self.dw_launches.append(("dw:" + (ops[0].get("group") or ops[0]["out"]), "fwd", pd, []))
                 prd = ctypes.byref(pd)
                 if live_bn:
                     pb, sums, bsums, ws, dys = self._bn_problem(ops)
@@ -1033,6 +1038,7 @@ class TrainEngine:
                      self.Pbf.data_ptr() + 2 * self.bf_off[name + ":w1"], self._pview(name + "/conv2d/bias").data_ptr(),
                      self.Pbf.data_ptr() + 2 * self.bf_off[name + ":w2"], self._pview(name + "/conv2d_1/bias").data_ptr(),
                      se["se"], state.data_ptr(), state.numel())
+                self.se_launches.append(("se:" + op["out"], "fwd", B, x.shape[1] * x.shape[2], se["C"], se["se"]))
                 self.fwd_steps.append(lambda st, a=a: _C.check(lib.rn_squeeze_excite_fwd(*a, st), "rn_squeeze_excite_fwd"))
             elif kind == "maxpool":
                 if op["out"] in self.fused_pools:   # written by the fused stem launch
@@ -1129,6 +1135,7 @@ class TrainEngine:
                      self._pview(name + "/conv2d/bias", self.G).data_ptr(),
                      self._pview(name + "/conv2d_1/kernel", self.G).data_ptr(),
                      self._pview(name + "/conv2d_1/bias", self.G).data_ptr(), self.se_ws.data_ptr(), self.se_ws.numel())
+                self.se_launches.append(("se:" + op["out"], "bwd", B, x.shape[1] * x.shape[2], se["C"], se["se"]))
                 se_bwd = lambda st, a=a: _C.check(lib.rn_squeeze_excite_bwd(*a, st), "rn_squeeze_excite_bwd")
                 se_bwd.writes = [name + sfx for sfx in ("/conv2d/kernel", "/conv2d/bias", "/conv2d_1/kernel", "/conv2d_1/bias")]
                 self.bwd_steps.append(se_bwd)
@@ -1505,6 +1512,7 @@ class TrainEngine:
             ws = torch.empty((max(lib.rn_depthwise_wgrad_workspace_bytes(ctypes.byref(p)), 256),), dtype=torch.uint8,
                              device=self.dev)
             self._keep += [p, ws]
+            self.dw_wgrad_launches.append(("dw_wgrad:" + dname, p))
             a = (ctypes.byref(p), self._pview(d["kvar"], self.G).data_ptr(), ws.data_ptr(), ws.numel())
             self.bwd_steps.append(self._side(lambda st, a=a: _C.check(lib.rn_depthwise_conv2d_nhwc_wgrad(*a, st),
                                                                      "dw wgrad"), writes=[d["kvar"]]))
@@ -1552,6 +1560,7 @@ class TrainEngine:
                 s.residual = None if first else gbuf.data_ptr()
                 s.N, s.H, s.W, s.C, s.Ho, s.Wo = B, H, W, d["C"], H, W
             self._keep.append(p)
+            self.dw_launches.append(("dw_dgrad:" + "+".join(o["out"] for o in sub), "dgrad", p, ups))
 
             def dgrad(st, p=p, ups=ups):
                 for u in ups:

@@ -83,8 +83,9 @@ def _close_bf16(got, want):
     assert (got != want).float().mean().item() < 0.03
 
 
-def _check_conv_launch(cuda, eng, name, p):
-    """re-issue one forward / data-gradient launch on fresh random tensors of its own geometry"""
+def _check_conv_launch(cuda, eng, name, p, close=_close_bf16):
+    """re-issue one forward / data-gradient launch on fresh random tensors of its own geometry; `close` compares a 16-bit
+    output with its rounded float64 reference (tests/test_gpu_bench_shapes_effnet.py: in steps of IEEE half)"""
     from retinanet import _C
     lib, h16 = eng.lib, eng.h16
     g = torch.Generator(device=cuda).manual_seed(zlib.crc32(name.encode()) % (2 ** 31))
@@ -201,7 +202,7 @@ def _check_conv_launch(cuda, eng, name, p):
             spread = (want - want.mean()).abs().max().item() + 1e-6
             assert (got - want).abs().max().item() <= 2e-4 * spread, (name, i)
         else:
-            _close_bf16(got, rb(yv).float())
+            close(got, rb(yv).float())
         stored = t["y"].double().reshape(-1, s.Cout)
         if "partial" in t and "bn_y" not in t:      # forward statistics of the STORED tensor
             part = t["partial"].double()

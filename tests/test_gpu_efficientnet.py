@@ -17,6 +17,42 @@ def _bf(x):
     return x.to(torch.bfloat16).to(torch.float32)
 
 
+# The 16-bit storage type of the kernel tests below (the pattern of tests/test_gpu_conv.py): a test parametrized with
+# build="f16" runs on librnet_hip_f16.so — the `mixed_float16` library configs[4] runs on — with IEEE-half tensors, and its
+# tolerances are the same number of storage steps (U = unit roundoff: 2^-8 bfloat16, 2^-11 half); every other test runs the
+# bfloat16 build with exactly its former bounds.
+H16 = torch.bfloat16
+_DT = {"bf16": torch.bfloat16, "f16": torch.float16}
+U = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
+BUILDS = ["bf16", "f16"]
+
+
+def _both_builds(cases):
+    """(build, *case) parameters: every case on the bfloat16 build under its former id, and on the half build (f16-...)"""
+    ids = ["-".join(str(v) for v in c) for c in cases]
+    return ([pytest.param("bf16", *c, id=i) for c, i in zip(cases, ids)] +
+            [pytest.param("f16", *c, id="f16-" + i) for c, i in zip(cases, ids)])
+
+
+@pytest.fixture(autouse=True)
+def _storage_type(request):
+    global H16
+    params = request.node.callspec.params if hasattr(request.node, "callspec") else {}
+    H16 = _DT[params.get("build", "bf16")]
+    yield
+    H16 = torch.bfloat16
+
+
+def _r16(x):
+    """round to the storage type under test"""
+    return x.to(H16).to(torch.float32)
+
+
+def _lib():
+    from retinanet import _C
+    return _C.lib(H16 == torch.float16)
+
+
 def _same(x, k, s):
     H, W = x.shape[2], x.shape[3]
     ph = max((-(-H // s) - 1) * s + k - H, 0)
@@ -24,34 +60,34 @@ def _same(x, k, s):
     return F.pad(x, (pw // 2, pw - pw // 2, ph // 2, ph - ph // 2)), ph // 2, pw // 2
 
 
-@pytest.mark.parametrize("N,H,W,C,k,s,act", [
+@pytest.mark.parametrize("build,N,H,W,C,k,s,act", _both_builds([
     (2, 32, 32, 144, 3, 1, "swish"), (2, 40, 40, 192, 5, 2, "swish"), (1, 20, 20, 816, 5, 1, "swish"),
-    (2, 16, 16, 160, 3, 1, None), (2, 13, 11, 48, 1, 1, None), (1, 33, 31, 96, 3, 2, "relu")])
-def test_depthwise_conv(cuda, N, H, W, C, k, s, act):
+    (2, 16, 16, 160, 3, 1, None), (2, 13, 11, 48, 1, 1, None), (1, 33, 31, 96, 3, 2, "relu")]))
+def test_depthwise_conv(cuda, build, N, H, W, C, k, s, act):
     from retinanet import _C
-    lib = _C.lib()
+    lib = _lib()
     g = torch.Generator().manual_seed(C + k)
-    x = _bf(torch.randn((N, H, W, C), generator=g))
+    x = _r16(torch.randn((N, H, W, C), generator=g))
     w = torch.randn((k, k, C, 1), generator=g) * (1.0 / k)
     scale = torch.rand(C, generator=g) + 0.5
     shift = torch.randn(C, generator=g) * 0.1
     xp, pt, pl = _same(x.permute(0, 3, 1, 2), k, s)
     # bf16 tensors between the layers (include/rnet_hip.h): DepthwiseConv2D output, BatchNorm output in front of swish
-    want = _bf(F.conv2d(xp, _bf(w).permute(2, 3, 0, 1).contiguous(), None, stride=s, groups=C))
+    want = _r16(F.conv2d(xp, _r16(w).permute(2, 3, 0, 1).contiguous(), None, stride=s, groups=C))
     want = want * scale[None, :, None, None] + shift[None, :, None, None]
     if act == "swish":
-        want = _bf(want)
+        want = _r16(want)
         want = want * torch.sigmoid(want)
     elif act == "relu":
         want = F.relu(want)
     want = want.permute(0, 2, 3, 1)
     Ho, Wo = want.shape[1], want.shape[2]
     st = _C.current_stream()
-    xd = x.to(cuda, torch.bfloat16).contiguous()
-    wd = torch.empty((k * k, C), dtype=torch.bfloat16, device=cuda)
+    xd = x.to(cuda, H16).contiguous()
+    wd = torch.empty((k * k, C), dtype=H16, device=cuda)
     wf = w.to(cuda).contiguous()
     _C.check(lib.rn_pack_depthwise_weight(_C.ptr(wf), k, C, _C.ptr(wd), st), "pack")
-    y = torch.empty((N, Ho, Wo, C), dtype=torch.bfloat16, device=cuda)
+    y = torch.empty((N, Ho, Wo, C), dtype=H16, device=cuda)
     sc, sh = scale.to(cuda), shift.to(cuda)
     p = _C.DwProblem()
     p.k, p.stride, p.pad_top, p.pad_left, p.act, p.num_segments = k, s, pt, pl, _C.ACT_IDS[act], 1
@@ -61,66 +97,66 @@ def test_depthwise_conv(cuda, N, H, W, C, k, s, act):
     _C.check(lib.rn_depthwise_conv2d_nhwc_fwd(ctypes.byref(p), st), "dw")
     torch.cuda.synchronize()
     got = y.float().cpu()
-    # fp32 accumulation in a different order + one bf16 rounding of the output
-    tol = 2.0 ** -7 * want.abs().clamp_min(1.0)
+    # fp32 accumulation in a different order + one 16-bit rounding of the output: one step
+    tol = 2 * U[H16] * want.abs().clamp_min(1.0)
     assert ((got - want).abs() <= tol).all(), (got - want).abs().max().item()
 
 
-@pytest.mark.parametrize("N,HW,C,se", [(2, 40 * 40, 144, 6), (3, 20 * 20, 816, 34), (1, 7 * 5, 2304, 96),
-                                         (2, 1, 40, 10)])
-def test_squeeze_excite(cuda, N, HW, C, se):
+@pytest.mark.parametrize("build,N,HW,C,se", _both_builds([(2, 40 * 40, 144, 6), (3, 20 * 20, 816, 34), (1, 7 * 5, 2304, 96),
+                                         (2, 1, 40, 10)]))
+def test_squeeze_excite(cuda, build, N, HW, C, se):
     from retinanet import _C
-    lib = _C.lib()
+    lib = _lib()
     g = torch.Generator().manual_seed(C)
-    x = _bf(torch.randn((N, HW, C), generator=g) + 0.3)
-    w1 = _bf(torch.randn((se, C), generator=g) * (2.0 / C) ** 0.5)
+    x = _r16(torch.randn((N, HW, C), generator=g) + 0.3)
+    w1 = _r16(torch.randn((se, C), generator=g) * (2.0 / C) ** 0.5)
     b1 = torch.randn(se, generator=g) * 0.1
-    w2 = _bf(torch.randn((C, se), generator=g) * (2.0 / se) ** 0.5)
+    w2 = _r16(torch.randn((C, se), generator=g) * (2.0 / se) ** 0.5)
     b2 = torch.randn(C, generator=g) * 0.1
     # every Keras layer output under the mixed policy is a 16-bit tensor: round where SE.call
     # (efficientnet.py:252-265) materialises one
-    pooled = _bf(x.mean(dim=1))
-    h = _bf(pooled @ w1.t() + b1)
-    h = _bf(h * torch.sigmoid(h))
-    gate = _bf(torch.sigmoid(_bf(h @ w2.t() + b2)))
+    pooled = _r16(x.mean(dim=1))
+    h = _r16(pooled @ w1.t() + b1)
+    h = _r16(h * torch.sigmoid(h))
+    gate = _r16(torch.sigmoid(_r16(h @ w2.t() + b2)))
     want = x * gate[:, None, :]
-    xd = x.to(cuda, torch.bfloat16).contiguous()
+    xd = x.to(cuda, H16).contiguous()
     ws = torch.empty(lib.rn_se_workspace_bytes(N, C), dtype=torch.uint8, device=cuda)
-    args = [t.to(cuda).contiguous() for t in (w1.to(torch.bfloat16), b1, w2.to(torch.bfloat16), b2)]
+    args = [t.to(cuda).contiguous() for t in (w1.to(H16), b1, w2.to(H16), b2)]
     _C.check(lib.rn_squeeze_excite_inplace(_C.ptr(xd), N, HW, C, _C.ptr(args[0]), _C.ptr(args[1]), _C.ptr(args[2]),
                                            _C.ptr(args[3]), se, _C.ptr(ws), ws.numel(), _C.current_stream()), "se")
     torch.cuda.synchronize()
     got = xd.float().cpu()
-    # a 1-ulp flip of an intermediate bf16 rounding moves the gate by <= 2^-8 relative
-    tol = 2.0 ** -6 * want.abs().clamp_min(0.05)
+    # a 1-ulp flip of an intermediate 16-bit rounding moves the gate by <= U relative
+    tol = 4 * U[H16] * want.abs().clamp_min(0.05)
     assert ((got - want).abs() <= tol).all(), (got - want).abs().max().item()
-    assert ((got - want).abs() <= 2.0 ** -8 * want.abs() + 1e-6).float().mean() > 0.97
+    assert ((got - want).abs() <= U[H16] * want.abs() + 1e-6).float().mean() > 0.97
 
 
-@pytest.mark.parametrize("N,H,W,C,k,s", [(2, 16, 16, 144, 3, 1), (2, 20, 20, 96, 5, 2), (1, 9, 7, 64, 5, 1),
+@pytest.mark.parametrize("build,N,H,W,C,k,s", _both_builds([(2, 16, 16, 144, 3, 1), (2, 20, 20, 96, 5, 2), (1, 9, 7, 64, 5, 1),
                                          (2, 12, 12, 48, 3, 2), (1, 8, 8, 160, 1, 1),
                                          # the weight gradient's workgroups cover min(C / channels-per-thread, 64) channel
                                          # groups: one group, a whole odd-sized pixel, several slabs with a short last one
                                          (1, 6, 6, 8, 3, 1), (2, 14, 14, 40, 3, 1), (1, 10, 10, 816, 5, 1),
-                                         (1, 6, 6, 1392, 5, 2), (1, 6, 6, 2304, 3, 1), (1, 8, 8, 288, 3, 2)])
-def test_depthwise_backward(cuda, N, H, W, C, k, s):
+                                         (1, 6, 6, 1392, 5, 2), (1, 6, 6, 2304, 3, 1), (1, 8, 8, 288, 3, 2)]))
+def test_depthwise_backward(cuda, build, N, H, W, C, k, s):
     """dgrad = the forward kernel on (zero-upsampled) dy with the tap-reversed filter; wgrad = the two-stage
     reduction kernel; both against torch autograd on the same bf16-rounded operands."""
     from retinanet import _C
-    lib = _C.lib()
+    lib = _lib()
     g = torch.Generator().manual_seed(C * k + s)
-    x = _bf(torch.randn((N, H, W, C), generator=g))
+    x = _r16(torch.randn((N, H, W, C), generator=g))
     w = torch.randn((k, k, C, 1), generator=g) * (1.0 / k)
     xp, pt, pl = _same(x.permute(0, 3, 1, 2), k, s)
     xa = x.double().requires_grad_(True)
-    wa = _bf(w).double().requires_grad_(True)
+    wa = _r16(w).double().requires_grad_(True)
     xpa, _, _ = _same(xa.permute(0, 3, 1, 2), k, s)
     ya = F.conv2d(xpa, wa.permute(2, 3, 0, 1), None, stride=s, groups=C).permute(0, 2, 3, 1)
     Ho, Wo = ya.shape[1], ya.shape[2]
-    dy = _bf(torch.randn((N, Ho, Wo, C), generator=g))
+    dy = _r16(torch.randn((N, Ho, Wo, C), generator=g))
     (ya * dy.double()).sum().backward()
     st = _C.current_stream()
-    xd, dyd = x.to(cuda, torch.bfloat16).contiguous(), dy.to(cuda, torch.bfloat16).contiguous()
+    xd, dyd = x.to(cuda, H16).contiguous(), dy.to(cuda, H16).contiguous()
     master = w.reshape(k * k, C).to(cuda).contiguous()          # f32 master [k*k][C]
     # ---- weight gradient
     p = _C.DwProblem()
@@ -135,14 +171,14 @@ def test_depthwise_backward(cuda, N, H, W, C, k, s):
     want_dw = wa.grad.reshape(k * k, C).float()
     torch.testing.assert_close(dw.cpu(), want_dw, rtol=2e-3, atol=2e-3 * want_dw.abs().max().item())
     # ---- data gradient
-    wflip = torch.empty((k * k, C), dtype=torch.bfloat16, device=cuda)
+    wflip = torch.empty((k * k, C), dtype=H16, device=cuda)
     _C.check(lib.rn_pack_depthwise_weight_flip(_C.ptr(master), k, C, _C.ptr(wflip), st), "flip")
     src = dyd
     if s == 2:
-        src = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=cuda)
+        src = torch.empty((N, H, W, C), dtype=H16, device=cuda)
         _C.check(lib.rn_upsample_zero2x(_C.ptr(dyd), _C.ptr(src), N, Ho, Wo, C, H, W, st), "up")
-    old = _bf(torch.randn((N, H, W, C), generator=g)).to(cuda, torch.bfloat16)   # an already written gradient
-    dx = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=cuda)
+    old = _r16(torch.randn((N, H, W, C), generator=g)).to(cuda, H16)   # an already written gradient
+    dx = torch.empty((N, H, W, C), dtype=H16, device=cuda)
     q = _C.DwProblem()
     q.k, q.stride, q.pad_top, q.pad_left, q.act, q.num_segments = k, 1, k - 1 - pt, k - 1 - pl, 0, 1
     sq = q.seg[0]
@@ -152,20 +188,20 @@ def test_depthwise_backward(cuda, N, H, W, C, k, s):
     torch.cuda.synchronize()
     want_dx = (xa.grad + old.float().cpu().double()).float()
     got = dx.float().cpu()
-    assert ((got - want_dx).abs() <= 2.0 ** -7 * want_dx.abs().clamp_min(0.5)).all(), (got - want_dx).abs().max().item()
+    assert ((got - want_dx).abs() <= 2 * U[H16] * want_dx.abs().clamp_min(0.5)).all(), (got - want_dx).abs().max().item()
 
 
-@pytest.mark.parametrize("N,HW,C,se", [(4, 20 * 20, 144, 6), (3, 10 * 10, 816, 34), (2, 49, 96, 4)])
-def test_squeeze_excite_train_forward_backward(cuda, N, HW, C, se):
+@pytest.mark.parametrize("build,N,HW,C,se", _both_builds([(4, 20 * 20, 144, 6), (3, 10 * 10, 816, 34), (2, 49, 96, 4)]))
+def test_squeeze_excite_train_forward_backward(cuda, build, N, HW, C, se):
     from retinanet import _C
-    lib = _C.lib()
+    lib = _lib()
     g = torch.Generator().manual_seed(C + 1)
-    x = _bf(torch.randn((N, HW, C), generator=g) + 0.3)
-    w1 = _bf(torch.randn((se, C), generator=g) * (2.0 / C) ** 0.5)
+    x = _r16(torch.randn((N, HW, C), generator=g) + 0.3)
+    w1 = _r16(torch.randn((se, C), generator=g) * (2.0 / C) ** 0.5)
     b1 = torch.randn(se, generator=g) * 0.1
-    w2 = _bf(torch.randn((C, se), generator=g) * (2.0 / se) ** 0.5)
+    w2 = _r16(torch.randn((C, se), generator=g) * (2.0 / se) ** 0.5)
     b2 = torch.randn(C, generator=g) * 0.1
-    dy = _bf(torch.randn((N, HW, C), generator=g))
+    dy = _r16(torch.randn((N, HW, C), generator=g))
     leaves = [t.double().requires_grad_(True) for t in (x, w1, b1, w2, b2)]
     xa, w1a, b1a, w2a, b2a = leaves
     h = xa.mean(dim=1) @ w1a.t() + b1a
@@ -175,8 +211,8 @@ def test_squeeze_excite_train_forward_backward(cuda, N, HW, C, se):
     (ya * dy.double()).sum().backward()
     st = _C.current_stream()
     dev = lambda t, dt=None: t.to(cuda, dt).contiguous() if dt else t.to(cuda).contiguous()
-    xd, dyd = dev(x, torch.bfloat16), dev(dy, torch.bfloat16)
-    w1d, w2d, b1d, b2d = dev(w1, torch.bfloat16), dev(w2, torch.bfloat16), dev(b1), dev(b2)
+    xd, dyd = dev(x, H16), dev(dy, H16)
+    w1d, w2d, b1d, b2d = dev(w1, H16), dev(w2, H16), dev(b1), dev(b2)
     nbytes = lib.rn_se_workspace_bytes(N, C)
     state = torch.empty(nbytes, dtype=torch.uint8, device=cuda)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=cuda)
@@ -190,14 +226,117 @@ def test_squeeze_excite_train_forward_backward(cuda, N, HW, C, se):
                                        _C.ptr(state), _C.ptr(dw1), _C.ptr(db1), _C.ptr(dw2), _C.ptr(db2), _C.ptr(ws),
                                        nbytes, st), "se bwd")
     torch.cuda.synchronize()
-    torch.testing.assert_close(yd.float().cpu(), ya.detach().float(), rtol=2 ** -6, atol=1e-2)
-    # the kernel differentiates through its bf16-rounded intermediates: compare direction and size
+    # (bfloat16: rtol 2^-6, atol 0.01; the same number of storage steps on half)
+    torch.testing.assert_close(yd.float().cpu(), ya.detach().float(), rtol=4 * U[H16], atol=2.56 * U[H16])
+    # the kernel differentiates through its 16-bit intermediates: compare direction and size (bfloat16: cosine > 0.999,
+    # norm ratio within 2 %)
     for name, got, want in (("dx", dx.float().cpu(), xa.grad), ("dw1", dw1.cpu(), w1a.grad), ("db1", db1.cpu(), b1a.grad),
                             ("dw2", dw2.cpu(), w2a.grad), ("db2", db2.cpu(), b2a.grad)):
         a, b = got.double().reshape(-1), want.reshape(-1)
         cos = float(torch.dot(a, b) / (a.norm() * b.norm() + 1e-30))
-        assert cos > 0.999, (name, cos)
-        assert abs(float(a.norm() / (b.norm() + 1e-30)) - 1.0) < 0.02, (name, float(a.norm() / b.norm()))
+        assert cos > 1 - 0.256 * U[H16], (name, cos)
+        assert abs(float(a.norm() / (b.norm() + 1e-30)) - 1.0) < 5.12 * U[H16], (name, float(a.norm() / b.norm()))
+
+
+# ---- the slab forms of the pooling / BatchNorm reductions that only the bench batch selected ----------------------------
+# bn_slab_plan / se_slab_plan leave the 64-channel slab only when (row chunks) x (slabs) reaches 512 workgroups; these
+# shapes are picked from the restated plans (tests/test_gpu_bench_shapes_effnet.py) so that each form runs on both builds.
+@pytest.mark.parametrize("N,HW,C,form", [(16, 32768, 144, (18, 1)), (16, 32768, 288, (36, 1)), (8, 24576, 288, (12, 3))],
+                         ids=["144ch-18x1", "288ch-36x1", "288ch-12x3"])
+@pytest.mark.parametrize("build", BUILDS)
+def test_squeeze_excite_slab_forms(cuda, build, N, HW, C, form):
+    """rn_squeeze_excite_fwd / _bwd on the one-slab and the multi-slab wide forms of se_pool_kernel / se_bwd_pool_kernel,
+    against float64 on the GPU with the 16-bit rounding points of include/rnet_hip.h"""
+    from retinanet import _C
+    from test_gpu_bench_shapes_effnet import check_se_backward, check_se_forward, se_plan, se_tensors
+    assert se_plan(N, HW, C) == form
+    lib, se = _lib(), C // 24
+    g = torch.Generator(device=cuda).manual_seed(C * 7 + N)
+    x, w1, b1, w2, b2, dy = se_tensors(cuda, g, N, HW, C, se, H16)
+    nbytes = lib.rn_se_workspace_bytes(N, C)
+    state = torch.full((nbytes,), 0xff, dtype=torch.uint8, device=cuda)
+    ws = torch.full((nbytes,), 0xff, dtype=torch.uint8, device=cuda)
+    y, dx = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
+    grads = [torch.full(shp, float("nan"), device=cuda) for shp in ((se, C), (se,), (C, se), (C,))]
+    st = _C.current_stream()
+    _C.check(lib.rn_squeeze_excite_fwd(_C.ptr(x), _C.ptr(y), N, HW, C, _C.ptr(w1), _C.ptr(b1), _C.ptr(w2), _C.ptr(b2), se,
+                                       _C.ptr(state), nbytes, st), "se fwd")
+    _C.check(lib.rn_squeeze_excite_bwd(_C.ptr(x), _C.ptr(dy), _C.ptr(dx), N, HW, C, _C.ptr(w1), _C.ptr(w2), se, _C.ptr(state),
+                                       *[_C.ptr(t) for t in grads], _C.ptr(ws), nbytes, st), "se bwd")
+    torch.cuda.synchronize()
+    check_se_forward(x, y, state, w1, b1, w2, b2, H16, "se")
+    check_se_backward(x, dy, dx, state, w1, w2, *grads, H16, "se")
+
+
+def _bn_case(P, C, act, rows_per_sample=0, residual=False, dres=False):
+    """an rn_bn_problem that only describes a geometry (the pointer fields are flags for
+    tests/test_gpu_bench_shapes_effnet.py::check_bn_problem_h16, which allocates its own tensors)"""
+    from retinanet import _C
+    p = _C.BnProblem()
+    p.num_segments, p.act, p.bessel, p.eps, p.momentum, p.count_scale = 1, _C.ACT_IDS[act], 1, 1e-3, 0.99, 1.0
+    s = p.seg[0]
+    s.P, s.C = P, C
+    s.residual, s.dres = (1 if residual else None), (1 if dres else None)
+    if rows_per_sample:
+        s.sample_scale, s.rows_per_sample = 1, rows_per_sample
+    return p
+
+
+@pytest.mark.parametrize("P,C,form", [(16384, 144, (18, 1)), (8192, 144, (9, 2)), (16384, 232, (15, 2))],
+                         ids=["144ch-18x1", "144ch-9x2", "232ch-15x2"])
+@pytest.mark.parametrize("kind", ["swish", "drop_connect"])
+@pytest.mark.parametrize("build", BUILDS)
+def test_batchnorm_slab_forms(cuda, build, kind, P, C, form):
+    """BatchNorm forward + backward (rn_bn_stats_finalize, rn_bn_apply, rn_bn_bwd_reduce, rn_bn_bwd_apply) on the wide slab
+    forms of bn_colreduce_kernel: a swish layer, and an MBConv project layer with its stochastic-depth factors and skip"""
+    from test_gpu_bench_shapes_effnet import bn_plan, check_bn_problem_h16
+    assert bn_plan(P, C) == form
+    if kind == "swish":
+        p = _bn_case(P, C, "swish")
+    else:
+        p = _bn_case(P, C, None, rows_per_sample=1024, residual=True, dres=True)
+    check_bn_problem_h16(cuda, _lib(), H16, p, f"bn {kind} {P}x{C}")
+
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_nonfinite_gradients_stay_nonfinite(cuda, build):
+    """An inf in the upstream gradient must reach the f32 parameter gradients of the depthwise, squeeze-excite and swish
+    BatchNorm layers (the dynamic loss scale skips a step on a non-finite gradient, rn_optim.hip)."""
+    from retinanet import _C
+    from test_gpu_bench_shapes_effnet import check_bn_problem_h16, se_tensors
+    lib, st = _lib(), _C.current_stream()
+    g = torch.Generator(device=cuda).manual_seed(5)
+    # depthwise weight gradient
+    N, H, W, C, k = 2, 20, 20, 144, 5
+    x = torch.randn((N, H, W, C), generator=g, device=cuda).to(H16)
+    dy = torch.randn((N, H, W, C), generator=g, device=cuda).to(H16)
+    dy[1, 7, 9, 100] = float("inf")
+    p = _C.DwProblem()
+    p.k, p.stride, p.pad_top, p.pad_left, p.act, p.num_segments = k, 1, 2, 2, 0, 1
+    s = p.seg[0]
+    s.x, s.y = x.data_ptr(), dy.data_ptr()
+    s.N, s.H, s.W, s.C, s.Ho, s.Wo = N, H, W, C, H, W
+    ws = torch.zeros(lib.rn_depthwise_wgrad_workspace_bytes(ctypes.byref(p)), dtype=torch.uint8, device=cuda)
+    dw = torch.zeros((k * k, C), device=cuda)
+    _C.check(lib.rn_depthwise_conv2d_nhwc_wgrad(ctypes.byref(p), _C.ptr(dw), _C.ptr(ws), ws.numel(), st), "dw wgrad")
+    # squeeze-excite
+    N, HW, C, se = 4, 400, 144, 6
+    x, w1, b1, w2, b2, dy = se_tensors(cuda, g, N, HW, C, se, H16)
+    dy[2, 17, 33] = float("inf")
+    nbytes = lib.rn_se_workspace_bytes(N, C)
+    state = torch.zeros((nbytes,), dtype=torch.uint8, device=cuda)
+    sws = torch.zeros((nbytes,), dtype=torch.uint8, device=cuda)
+    y, dx = torch.empty_like(x), torch.empty_like(x)
+    grads = [torch.zeros(shp, device=cuda) for shp in ((se, C), (se,), (C, se), (C,))]
+    _C.check(lib.rn_squeeze_excite_fwd(_C.ptr(x), _C.ptr(y), N, HW, C, _C.ptr(w1), _C.ptr(b1), _C.ptr(w2), _C.ptr(b2), se,
+                                       _C.ptr(state), nbytes, st), "se fwd")
+    _C.check(lib.rn_squeeze_excite_bwd(_C.ptr(x), _C.ptr(dy), _C.ptr(dx), N, HW, C, _C.ptr(w1), _C.ptr(w2), se, _C.ptr(state),
+                                       *[_C.ptr(t) for t in grads], _C.ptr(sws), nbytes, st), "se bwd")
+    torch.cuda.synchronize()
+    assert not torch.isfinite(dw).all()
+    assert not torch.isfinite(grads[0]).all() and not torch.isfinite(grads[2]).all()
+    # swish BatchNorm: dgamma / dbeta (asserted inside)
+    check_bn_problem_h16(cuda, lib, H16, _bn_case(16384, 144, "swish"), "bn swish inf", dz_inf=True)
 
 
 def _randomize(model, seed):
