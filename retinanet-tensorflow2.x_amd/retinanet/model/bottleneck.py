@@ -7,8 +7,8 @@ group's first block, :220-228), relu.  With every BatchNorm folded (serving; the
 configs, model/builder.py:28-29) the 64-channel intermediates are pure HBM traffic: the fused launch keeps them on chip.
 
 `find_blocks(graph)` recognises the pattern structurally (kernel sizes, strides, channel counts, activations, who reads the
-intermediate tensors) — it does not depend on layer names; the engines add their own eligibility test (frozen / no gradient
-needed) and `Bottleneck64.supported()` asks the library about the shape.  RNET_FUSE_BOTTLENECK=0 keeps the per-layer launches."""
+intermediate tensors) — it does not depend on layer names; `fused_blocks()` adds the engine's own eligibility test (frozen /
+no gradient needed) and asks the library about the shape.  RNET_FUSE_BOTTLENECK=0 keeps the per-layer launches."""
 from __future__ import annotations
 
 import ctypes
@@ -17,18 +17,7 @@ import os
 import torch
 
 from retinanet import _C
-
-
-def _reads(op):
-    """tensor names an op reads"""
-    out = []
-    for k in ("inp", "residual", "tensor"):
-        if isinstance(op.get(k), str):
-            out.append(op[k])
-    for k in ("ins", "tensors"):
-        if isinstance(op.get(k), (list, tuple)):
-            out += [t for t in op[k] if isinstance(t, str)]
-    return out
+from .forward import fold_bn, tensor_readers
 
 
 def find_blocks(g):
@@ -36,10 +25,7 @@ def find_blocks(g):
     if os.environ.get("RNET_FUSE_BOTTLENECK", "1") == "0":
         return []
     by_out = {o["out"]: o for o in g.ops if o["op"] == "conv"}
-    readers = {}
-    for o in g.ops:
-        for t in _reads(o):
-            readers.setdefault(t, []).append(o)
+    readers = tensor_readers(g.ops)
     net_outs = {n for d in getattr(g, "outputs", {}).values() for n in d.values()}
     idx = {id(o): i for i, o in enumerate(g.ops)}
 
@@ -74,26 +60,30 @@ def find_blocks(g):
         # the intermediates must be private to the block
         inner = [a["out"], b["out"]] + ([sc["out"]] if sc else [])
         mine = {id(a), id(b), id(out)} | ({id(sc)} if sc else set())
-        if any(t in net_outs or any(id(r) not in mine for r in readers.get(t, [])) for t in inner):
+        if any(t in net_outs or any(id(r) not in mine for r, _ in readers.get(t, [])) for t in inner):
             continue
         ops = sorted([o for o in (sc, a, b, out) if o is not None], key=lambda o: idx[id(o)])
         blocks.append(dict(name=out["out"], ops=ops, a=a, b=b, out=out, sc=sc, x=x, Cx=Cx))
     return blocks
 
 
+def fused_blocks(lib, g, B, eligible):
+    """The blocks of find_blocks(g) that run as one launch: the engine's rule `eligible(blk)`, a half-precision block input
+    and a shape the kernel takes (rn_bottleneck64_supported)"""
+    return [blk for blk in find_blocks(g) if eligible(blk) and g.tensors[blk["x"]][3] == "bf16"
+            and lib.rn_bottleneck64_supported(int(B), *g.tensors[blk["x"]][:3]) == 1]
+
+
 class Bottleneck64:
     """One fused block of one engine: packed weights, folded BatchNorm vectors (stable addresses: a captured HIP graph or a
     launch list keeps them), the launch descriptor."""
 
-    def __init__(self, lib, g, blk, B, dev, h16, launch_opts, x_tensor, y_tensor):
+    def __init__(self, lib, g, blk, B, dev, launch_opts, x_tensor, y_tensor):
+        """blk: one of fused_blocks(); x_tensor / y_tensor: the block's input and output buffers"""
         self.lib, self.g, self.blk, self.B, self.dev = lib, g, blk, int(B), dev
         H, W, Cx, _ = g.tensors[blk["x"]]
         self.H, self.W, self.Cx = H, W, Cx
         self.name = "bneck:" + blk["name"]
-        self.ok = (x_tensor.dtype == h16 and x_tensor.is_contiguous() and y_tensor.is_contiguous()
-                   and lib.rn_bottleneck64_supported(self.B, H, W, Cx) == 1)
-        if not self.ok:
-            return
         self.packed = torch.empty((lib.rn_bottleneck64_packed_bytes(Cx),), dtype=torch.uint8, device=dev)
         self.affine = torch.zeros((4 * 64 + (4 if Cx == 64 else 2) * 256,), dtype=torch.float32, device=dev)
         p = _C.Bottleneck64Problem()
@@ -119,10 +109,7 @@ class Bottleneck64:
                                               _C.current_stream()), "rn_bottleneck64_pack")
         parts = []
         for op in [blk["a"], blk["b"], blk["out"]] + ([blk["sc"]] if blk["sc"] else []):
-            bn = op["bn"]
-            f = lambda n: variables[bn + n].to(self.dev, torch.float32)
-            scale = f("/gamma") / torch.sqrt(f("/moving_variance") + eps)
-            parts += [scale, f("/beta") - f("/moving_mean") * scale]
+            parts += fold_bn(variables, op["bn"], None, eps, self.dev)[:2]
         self.affine.copy_(torch.cat(parts))
         self._keep = (wa, wb, wo, ws)          # the pack kernel reads them asynchronously
 

@@ -23,6 +23,7 @@ import torch
 from retinanet.dataloader.anchor_generator import AnchorBoxGenerator
 from retinanet.losses import RetinaNetLoss
 from retinanet.model.engine import InferenceEngine
+from retinanet.model.forward import half_activations
 from retinanet.model.graph import build_retinanet_graph, init_variables
 from retinanet.model.layers import DetectionPostProcess
 
@@ -175,8 +176,7 @@ class RetinaNetModel:
             self._engines[key] = InferenceEngine(self.graph, self.variables, batch_size, self.device,
                                                  bn_epsilon=self.params.architecture.batch_norm.epsilon,
                                                  capture_graph=capture_graph,
-                                                 f16=(str(self.params.floatx.precision) == "mixed_float16"
-                                                      and os.environ.get("RNET_F16", "1") != "0"),
+                                                 f16=half_activations(self.params),
                                                  launch_opts=self.launch_opts)
         return self._engines[key]
 

@@ -32,7 +32,9 @@ import numpy as np
 import torch
 
 from retinanet import _C
-from .engine import split_by_depth
+from .bottleneck import Bottleneck64, fused_blocks
+from .forward import (FoldedConvs, conv_launch_name, conv_problem, dw_problem, half_activations, maxpool_step, split_by_depth,
+                      stem_input, stem_pool_partner, stem_pool_step, stem_problem, tensor_readers, topdown_step)
 
 _DT = {"bf16": torch.bfloat16, "f32": torch.float32}
 _SEG_DTYPE = np.dtype([("offset", "<i8"), ("size", "<i8"), ("wd", "<i4"), ("bb", "<i4"), ("nb", "<i4"),
@@ -72,10 +74,7 @@ class TrainEngine:
         self.params_cfg = model.params
         self.B = int(batch_size)
         self.dev = model.device
-        # `mixed_float16` (BASELINE config 5): IEEE-half activations / packed weights on librnet_hip_f16.so + the
-        # LossScaleOptimizer arithmetic of optimizer_step; RNET_F16=0 keeps bfloat16 storage under that policy
-        self.f16 = (str(getattr(getattr(model.params, "floatx", None), "precision", "")) == "mixed_float16"
-                    and os.environ.get("RNET_F16", "1") != "0")
+        self.f16 = half_activations(model.params)    # (+ the LossScaleOptimizer arithmetic of optimizer_step)
         self.h16 = torch.float16 if self.f16 else torch.bfloat16
         self._DT = {"bf16": self.h16, "f32": torch.float32}
         self.lib = _C.lib(self.f16)
@@ -103,7 +102,6 @@ class TrainEngine:
             wide_pred_terms = os.environ.get("RNET_TRAIN_PRED_W_TERMS") or \
                 getattr(getattr(model.params, "training", None), "prediction_weight_planes", None) or 2
         self.wide_pred_terms = max(1, min(int(wide_pred_terms), _C.PRED_W_TERMS))
-        self._pair_cache = {}
         self.frozen = set(frozen_names)
         for k in model.variables:
             if any(rx.search(k) for rx in frozen_regexes):
@@ -166,6 +164,11 @@ class TrainEngine:
             # launch runs on the main stream, in order, so one workspace serves them all; attached at creation because the
             # dispatcher looks at it
             self.splitk_ws = _C.new_splitk_workspace(self.lib, self.dev)
+            # inference form (frozen conv and BatchNorm, no gradient needed at the input): packed weights and folded
+            # BatchNorm at stable addresses; the same rule decides the pixel-pair form, so a raw (pre-BN) launch never
+            # sees pair-packed weights
+            self.folded = FoldedConvs(self.lib, self.g, self.B, self.dev, self.h16, self.launch_opts, self.splitk_ws,
+                                      self.eps, eligible=self._inference_form)
             self._analyse()
             self._alloc_params()
             self._alloc_tensors()
@@ -200,6 +203,7 @@ class TrainEngine:
             if o["op"] in ("topdown",):
                 o["ins"] = [alias.get(n, n) for n in o["ins"]]
             self.ops.append(o)
+        self.readers = tensor_readers(self.ops)
         # variable name -> (kind, layer): conv / dw / se1 / se2 kernels are weight-decayed
         # (executor.py:308-327: every trainable variable with 'kernel' in its name)
         self.var_kind = {}
@@ -222,6 +226,9 @@ class TrainEngine:
 
     def _bn_trainable(self, op):
         return op.get("bn") and (op["bn"] + "/gamma") not in self.frozen
+
+    def _inference_form(self, op):
+        return not self._conv_trainable(op) and not self._bn_trainable(op) and not self.requires.get(op["inp"])
 
     def _analyse(self):
         self.requires = {"images": False}
@@ -284,7 +291,7 @@ class TrainEngine:
                     pass                                        # first-layer conv: its own packed form
                 elif layer in f32_convs and self._f32_terms(layer) > 1:
                     cinp = lib.rn_conv_cin_pad(c["cin"])        # detection_head.py:80-88: the layer keeps its f32 kernel
-                    if self._pair_form(layer):                  # narrow layer (box prediction): the planes along Cout
+                    if self.folded.w_pair(layer):               # narrow layer (box prediction): the planes along Cout
                         buf = torch.zeros((lib.rn_conv_pair_rows(c["cout"]), c["k"], c["k"], cinp), dtype=self.h16,
                                           device=self.dev)
                         self.pair_packs.add(layer)
@@ -392,9 +399,6 @@ class TrainEngine:
                                                         c["cout"], cinp, self._f32_terms(self.var_kind[kname][1]),
                                                         buf.data_ptr(), st), "rn_pack_conv_weight_split")
 
-    def refresh_stem_pack(self):
-        self.refresh_packs()
-
     def _keras_layout(self, k, arena):
         """Variable `k` of a flat arena in the layout Keras holds it (conv / SE kernels HWIO)."""
         v = self.model.variables[k]
@@ -474,17 +478,21 @@ class TrainEngine:
     def _alloc_tensors(self):
         B, dev = self.B, self.dev
         self.t, self.raw, self.grad = {}, {}, {}
+        # frozen ResNet stage-1 bottleneck blocks as ONE launch each (retinanet/model/bottleneck.py): every layer of the
+        # block frozen with its BatchNorm, nothing below it needs a gradient; their inner tensors get no buffer
+        mine = {o["out"]: o for o in self.ops if "out" in o}
+        blocks = fused_blocks(self.lib, self.g, B, lambda blk: not self.requires.get(blk["x"]) and all(
+            o["out"] in mine and self._inference_form(mine[o["out"]]) and not self.requires.get(o["out"])
+            for o in blk["ops"]))
+        self._bneck_skip = {o["out"] for blk in blocks for o in blk["ops"]}
+        inner = self._bneck_skip - {blk["name"] for blk in blocks}
         for name, (H, W, C, dt) in self.tensors.items():
-            self.t[name] = torch.empty((B, H, W, C), dtype=self._DT[dt], device=dev)
-        # first-layer conv: zero-bordered bf16 NHWC4 copy of the image (rn_pack_image_nhwc4)
-        stem = self._stem_op()
-        Hs, Ws = self.tensors[stem["out"]][:2]
-        self.stem_k = stem.get("k", 7)
-        self.stem_pad = (stem.get("pad_top", 3), stem.get("pad_left", 3))
-        H, W, _, _ = self.tensors["images"]
-        self.Hp = max((Hs - 1) * 2 + self.stem_k, H + self.stem_pad[0])
-        self.Wp = -(-max((Ws - 1) * 2 + 8, W + self.stem_pad[1]) // 8) * 8
-        self.stem_in = torch.empty((B, self.Hp, self.Wp, 4), dtype=self.h16, device=dev)
+            if name not in inner:
+                self.t[name] = torch.empty((B, H, W, C), dtype=self._DT[dt], device=dev)
+        self.bneck = {blk["ops"][0]["out"]: Bottleneck64(self.lib, self.g, blk, B, dev, self.launch_opts, self.t[blk["x"]],
+                                                         self.t[blk["name"]]) for blk in blocks}
+        self.stem_k, self.stem_pad, self.Hp, self.Wp, self.stem_in = stem_input(self.tensors, self._stem_op(), B, self.h16,
+                                                                                dev)
         for op in self.ops:
             if op["op"] in ("conv", "stem", "dwconv") and self._bn_trainable(op):
                 self.raw[op["out"]] = torch.empty_like(self.t[op["out"]])
@@ -532,75 +540,12 @@ class TrainEngine:
                                      "mv": self.model.variables[bn + "/moving_variance"].to(dev, torch.float32).clone()}
 
     def _fold_frozen(self):
-        """inference-mode scale/shift + packed weights for frozen conv(+BN) layers."""
-        lib, v = self.lib, self.model.variables
-        st = _C.current_stream()
-        old_fold, old_packed = getattr(self, "fold", None), getattr(self, "packed_frozen", None)
-        self.fold, self.packed_frozen = {}, {}
+        """inference-mode scale/shift + packed weights for frozen conv(+BN) layers (in place after the first call)."""
         for op in self.ops:
-            if op["op"] not in ("conv", "stem") or self._conv_trainable(op):
-                continue
-            cname = op["conv"]
-            c = self.g.convs[cname]
-            w = v[self._kvar(op)].to(self.dev, torch.float32).contiguous()
-            cp = lib.rn_conv_cout_pad(c["cout"])
-            if op["op"] == "stem":
-                buf = torch.empty((cp, c["k"], 32), dtype=self.h16, device=self.dev)
-                _C.check(lib.rn_pack_stem_weight_rs(_C.ptr(w), c["k"], c["k"], c["cout"], _C.ptr(buf), st),
-                         "rn_pack_stem_weight_rs")
-            elif self._pixel_pair(op):     # 64-channel 3x3 layer as a 128 -> 128 convolution over pixel pairs (engine.pixel_pair_ok)
-                from .engine import pixel_pair_kernel
-                w2 = pixel_pair_kernel(w).contiguous()
-                cinp = lib.rn_conv_cin_pad(2 * c["cin"])
-                buf = torch.empty((lib.rn_conv_cout_pad(2 * c["cout"]), 3, 3, cinp), dtype=self.h16, device=self.dev)
-                _C.check(lib.rn_pack_conv_weight(_C.ptr(w2), 3, 3, 2 * c["cin"], 2 * c["cout"], cinp, _C.ptr(buf), st),
-                         "rn_pack_conv_weight")
-            else:
-                cinp = lib.rn_conv_cin_pad(c["cin"])
-                buf = torch.empty((cp, c["k"], c["k"], cinp), dtype=self.h16, device=self.dev)
-                _C.check(lib.rn_pack_conv_weight(_C.ptr(w), c["k"], c["k"], c["cin"], c["cout"], cinp,
-                                                 _C.ptr(buf), st), "rn_pack_conv_weight")
-            self.packed_frozen[cname] = buf
-            bias = v.get(cname + "/bias")
-            scale = shift = None
-            if op.get("bn"):
-                bn = op["bn"]
-                gmm, bta = v[bn + "/gamma"].to(self.dev).float(), v[bn + "/beta"].to(self.dev).float()
-                mean, var = v[bn + "/moving_mean"].to(self.dev).float(), v[bn + "/moving_variance"].to(self.dev).float()
-                scale = (gmm / torch.sqrt(var + self.eps)).contiguous()
-                shift = (bta - mean * scale).contiguous()
-            # the Conv2D bias stays separate: it is added before the layer's output is rounded (rn_conv_segment)
-            bias = None if bias is None else bias.to(self.dev).float().contiguous()
-            if op["op"] == "conv" and self._pixel_pair(op):     # per-channel vectors once per pixel of the pair
-                scale, shift, bias = [None if t is None else t.repeat(2).contiguous() for t in (scale, shift, bias)]
-            self.fold[op["out"]] = (scale, shift, bias)
-        # frozen ResNet stage-1 bottleneck blocks as ONE launch each (retinanet/model/bottleneck.py): every layer of the block
-        # frozen with its BatchNorm, nothing below it needs a gradient
-        if getattr(self, "bneck", None) is None:
-            from .bottleneck import Bottleneck64, find_blocks
-            self.bneck, self._bneck_skip = {}, set()
-            mine = {o["out"]: o for o in self.ops if "out" in o}
-            for blk in find_blocks(self.g):
-                ops_ = [mine.get(o["out"]) for o in blk["ops"]]
-                if any(o is None or self._conv_trainable(o) or self._bn_trainable(o) or self.requires.get(o["out"])
-                       for o in ops_) or self.requires.get(blk["x"]):
-                    continue
-                fb = Bottleneck64(lib, self.g, blk, self.B, self.dev, self.h16, self.launch_opts, self.t[blk["x"]],
-                                  self.t[blk["name"]])
-                if fb.ok:
-                    self.bneck[blk["ops"][0]["out"]] = fb
-                    self._bneck_skip.update(o["out"] for o in blk["ops"])
+            if op["op"] in ("conv", "stem") and not self._conv_trainable(op) and op["out"] not in self._bneck_skip:
+                self.folded.load(self.model.variables, op)
         for fb in self.bneck.values():
-            fb.load(v, self.eps)
-        if old_fold is not None:
-            # a refold after a restore: the launch descriptors hold the first buffers' addresses -> copy in place
-            for k, buf in self.packed_frozen.items():
-                old_packed[k].copy_(buf)
-            for k, new3 in self.fold.items():
-                for dst, src in zip(old_fold[k], new3):
-                    if dst is not None:
-                        dst.copy_(src)
-            self.fold, self.packed_frozen = old_fold, old_packed
+            fb.load(self.model.variables, self.eps)
 
     # ---- helpers to build launches ---------------------------------------------------------------------
     def _conv_meta(self, p):
@@ -642,6 +587,18 @@ class TrainEngine:
             variant = "conv_fwd_kernel<128,128,64,bf16>"
         return flops, byts, variant
 
+    def _timed(self, launch, *sinks):
+        """launch() between two timing events on the current stream (bench.py's profiles): (e0, e1, *row) goes to every
+        (list, row) of `sinks` whose list is not None"""
+        cur = torch.cuda.current_stream(self.dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(cur)
+        launch()
+        e1.record(cur)
+        for lst, row in sinks:
+            if lst is not None:
+                lst.append((e0, e1) + row)
+
     def _launch_conv(self, p, st, what):
         """All implicit-GEMM launches (forward and dgrad) go through here so bench.py can bracket the
         dominant kernel variant with HIP events on the launch stream."""
@@ -649,70 +606,32 @@ class TrainEngine:
         if prof is not None or lprof is not None:
             flops, byts, variant = self._conv_meta(p)
             if variant or lprof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                _C.check(self.lib.rn_conv2d_nhwc_fwd(ctypes.byref(p), st), what)
-                e1.record()
-                if prof is not None and variant:
-                    prof.append((e0, e1, flops, byts, variant))
+                lrow = None
                 if lprof is not None:
                     if getattr(self, "_launch_names", None) is None or len(self._launch_names) != len(self.conv_launches):
                         self._launch_names = {id(q): n for n, q in self.conv_launches}
                     kid = self.lib.rn_conv_kernel_id(ctypes.byref(p))
                     kname = variant or ("conv_fwd_kernel (128-row tiles)" if kid == 0 else f"kernel id {kid}")
-                    lprof.append((e0, e1, self._launch_names.get(id(p), what), flops, byts, kname))
+                    lrow = (self._launch_names.get(id(p), what), flops, byts, kname)
+                self._timed(lambda: _C.check(self.lib.rn_conv2d_nhwc_fwd(ctypes.byref(p), st), what),
+                            (prof if variant else None, (flops, byts, variant)), (lprof, lrow))
                 return
         _C.check(self.lib.rn_conv2d_nhwc_fwd(ctypes.byref(p), st), what)
 
     def _weight_ptr(self, cname):
-        if cname in self.packed_frozen:
-            return self.packed_frozen[cname].data_ptr()
+        """compute copy of the kernel of a live conv"""
         if cname in self.fwd_pack_of:
             return self.fwd_pack_of[cname].data_ptr()
         if cname in self.split_pack_of:
             return self.split_pack_of[cname].data_ptr()
         return self.Pbf.data_ptr() + 2 * self.bf_off[cname]
 
-    def _pixel_pair(self, op):
-        """True when the FROZEN conv `op` (inference form) runs as a convolution over pixel pairs (engine.pixel_pair_ok)"""
-        from .engine import pixel_pair_ok
-        self._ppair = getattr(self, "_ppair", {})
-        key = op["out"]
-        if key not in self._ppair:
-            # tied to the inference-form launch: a frozen kernel in front of a LIVE BatchNorm (custom freeze regexes) goes
-            # through _conv_problem(raw_mode=True), which keeps the layer's own shape — its weights must then not be the
-            # pair-packed [128,3,3,128] buffer (ADVICE r5)
-            ok = (op["op"] == "conv" and not self._conv_trainable(op) and not self._bn_trainable(op)
-                  and not self.requires.get(op["inp"]))
-            self._ppair[key] = ok and pixel_pair_ok(self.lib, self.g, op, self.B, self.launch_opts, getattr(self, "splitk_ws", None))
-        return self._ppair[key]
-
     def _f32_terms(self, layer):
         """bf16 weight planes of the dtype=float32 conv `layer` in THIS engine's forward pass: the narrow (pair-form)
         layers always carry both planes, the wide one `wide_pred_terms`"""
         if _C.PRED_W_TERMS <= 1:
             return 1
-        return _C.PRED_W_TERMS if self._pair_form(layer) else self.wide_pred_terms
-
-    def _pair_form(self, layer):
-        if layer not in self._pair_cache:
-            self._pair_cache[layer] = self._pair_form_uncached(layer)
-        return self._pair_cache[layer]
-
-    def _pair_form_uncached(self, layer):
-        """True when the f32 conv `layer` (one kernel shared by the pyramid levels of a grouped launch) is narrow enough that
-        its two weight planes go along Cout (rn_conv_segment.w_pair): 36 box-regression channels fill 72 of the 128 columns
-        of the halo kernel's 512 x 128 tiles; along Cin they were a 64-column tile of the 128-row kernel at 2 x the K depth."""
-        c = self.g.convs[layer]
-        if self.lib.rn_conv_cout_pad(c["cout"]) > 64:
-            return False                                        # wide layers (class prediction) already run 256-row tiles
-        ops = [o for o in self.ops if o["op"] == "conv" and o["conv"] == layer]
-        groups = {o.get("group") for o in ops}
-        if len(groups) != 1 or None in groups:
-            return False
-        shapes = [self.tensors[o["inp"]][:2] + (self.tensors[o["inp"]][2],) + self.tensors[o["out"]][:2] for o in ops]
-        return _C.pair_form_kernel(self.lib, self.B, c["k"], c["stride"], ops[0]["pad"], c["cin"], c["cout"], shapes,
-                                   self.launch_opts) > 0
+        return _C.PRED_W_TERMS if self.folded.w_pair(layer) else self.wide_pred_terms
 
     def _group_ops(self, kind, grp):
         """The ops of one grouped launch, in graph order.  (The one group that mixes K depths — the FPN lateral 1x1 convs with
@@ -722,63 +641,32 @@ class TrainEngine:
 
     def _conv_problem(self, ops, dst_of, raw_mode):
         """forward conv launch over `ops`; raw_mode: write pre-BN output (+bias) without activation."""
-        first = ops[0]
-        c0 = self.g.convs[first["conv"]]
-        assert not (raw_mode and any(self._pixel_pair(o) for o in ops)), "pair-packed weights behind a raw (pre-BN) launch"
-        p = _C.attach_splitk_workspace(_C.ConvProblem(), self.splitk_ws)
-        p.opts = self.launch_opts
-        p.R = p.S = c0["k"]
-        p.stride_h = p.stride_w = c0["stride"]
-        p.pad_top = p.pad_left = first["pad"]
-        p.act = _C.RN_ACT_NONE if raw_mode else _C.ACT_IDS[first["act"]]
-        p.out_dtype = _C.RN_DT_F32 if first["out_dtype"] == "f32" else _C.RN_DT_BF16
-        p.num_segments = len(ops)
+        p = conv_problem(self.g, ops, self.B, self.launch_opts, self.splitk_ws, lambda o: self._src(o["inp"]), dst_of,
+                         self.folded.pixel_pair, _C.RN_ACT_NONE if raw_mode else None)
         for i, op in enumerate(ops):
-            c = self.g.convs[op["conv"]]
-            x, y = self._src(op["inp"]), dst_of(op)
             s = p.seg[i]
-            s.x, s.w, s.y = x.data_ptr(), self._weight_ptr(op["conv"]), y.data_ptr()
-            s.scale = s.shift = s.bias = s.residual = None
             if raw_mode or self._conv_trainable(op):   # raw pre-BN output, or a live conv without BN (prediction convs)
-                s.bias = self._pview(op["conv"] + "/bias").data_ptr() if c["bias"] else None
+                s.w = self._weight_ptr(op["conv"])
+                s.bias = self._pview(op["conv"] + "/bias").data_ptr() if self.g.convs[op["conv"]]["bias"] else None
+                if not raw_mode:
+                    s.residual = self.t[op["residual"]].data_ptr() if op.get("residual") else None
+                s.w_terms = self._f32_terms(op["conv"]) if op["conv"] in self.split_pack_of and op["conv"] not in self.pair_packs else 1
+                s.w_pair = 1 if op["conv"] in self.pair_packs else 0
             else:
-                sc, sh, bs = self.fold[op["out"]]
-                s.scale = sc.data_ptr() if sc is not None else None
-                s.shift = sh.data_ptr() if sh is not None else None
-                s.bias = bs.data_ptr() if bs is not None else None
-            if not raw_mode:
-                s.residual = self.t[op["residual"]].data_ptr() if op.get("residual") else None
-            s.w_terms = self._f32_terms(op["conv"]) if op["conv"] in self.split_pack_of and op["conv"] not in self.pair_packs else 1
-            s.w_pair = 1 if op["conv"] in self.pair_packs else 0
-            s.N, s.H, s.W, s.Cin, s.pix_stride = self.B, x.shape[1], x.shape[2], c["cin"], x.shape[3]
-            s.Ho, s.Wo, s.Cout = y.shape[1], y.shape[2], c["cout"]
-            if not raw_mode and self._pixel_pair(op):      # the same bytes as [N, H, W/2, 2C]; algorithmic work: the layer's own
+                self.folded.fill(s, op, self.t)
+            if self.folded.pixel_pair(op):      # algorithmic work: the layer's own
+                c, x, y = self.g.convs[op["conv"]], self._src(op["inp"]), dst_of(op)
                 self._algo[id(p)] = (2 * self.B * y.shape[1] * y.shape[2] * 9 * c["cin"] * c["cout"],
                                      2 * x.numel() + 2 * y.numel() + 2 * 9 * c["cin"] * c["cout"])
-                s.W, s.Wo, s.Cin, s.Cout, s.pix_stride = x.shape[2] // 2, y.shape[2] // 2, 2 * c["cin"], 2 * c["cout"], 2 * x.shape[3]
         self._keep.append(p)
-        name = "fwd:" + (first.get("group") or first["out"])
-        if any(n == name for n, _ in self.conv_launches):   # second launch of a split group (engine.split_by_depth)
-            name += ":rest"
-        self.conv_launches.append((name, p))
+        self.conv_launches.append((conv_launch_name("fwd:", ops, {n for n, _ in self.conv_launches}), p))
         return p
 
     def _dw_problem(self, ops, dst_of):
         """forward depthwise launch over `ops` writing the raw (pre-BN) or final output; bf16 weights are
         the plain-cast copies of the [k*k][C] masters."""
-        d0 = self.g.dws[ops[0]["dw"]]
-        p = _C.DwProblem()
-        p.k, p.stride, p.pad_top, p.pad_left = d0["k"], d0["stride"], ops[0]["pad_top"], ops[0]["pad_left"]
-        p.act, p.num_segments = _C.RN_ACT_NONE, len(ops)
-        for i, op in enumerate(ops):
-            d = self.g.dws[op["dw"]]
-            if (d["k"], d["stride"], op["pad_top"], op["pad_left"]) != (p.k, p.stride, p.pad_top, p.pad_left):
-                raise ValueError("depthwise group mixes shapes")
-            x, y = self._src(op["inp"]), dst_of(op)
-            s = p.seg[i]
-            s.x, s.w, s.y = x.data_ptr(), self.Pbf.data_ptr() + 2 * self.bf_off["dw:" + op["dw"]], y.data_ptr()
-            s.scale, s.shift, s.residual = None, None, None
-            s.N, s.H, s.W, s.C, s.Ho, s.Wo = self.B, x.shape[1], x.shape[2], d["C"], y.shape[1], y.shape[2]
+        p = dw_problem(self.g, ops, self.B, lambda o: self._src(o["inp"]), dst_of,
+                       lambda o: self.Pbf.data_ptr() + 2 * self.bf_off["dw:" + o["dw"]], _C.RN_ACT_NONE)
         self._keep.append(p)
         return p
 
@@ -810,11 +698,7 @@ class TrainEngine:
                 byts += n * 2 + gate
             else:
                 byts += n * 2 + gate + n * (1 + ((2 if s.dres_accumulate else 1) if s.dres else 0))
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream(self.dev))
-        fn()
-        e1.record(torch.cuda.current_stream(self.dev))
-        prof.append((e0, e1, kind, byts))
+        self._timed(fn, (prof, (kind, byts)))
 
     def _bn_stats_finalize(self, prb, ws, sums, st):
         """Batch statistics -> (mean, invstd, scale, shift) + moving statistics.  One replica: the final reduction
@@ -914,30 +798,15 @@ class TrainEngine:
             if kind == "stem":
                 img, y = self.t["images"], self.t[op["out"]]
                 H, W = img.shape[1], img.shape[2]
-                c = self.g.convs[op["conv"]]
+                cout = self.g.convs[op["conv"]]["cout"]
                 pin = self.stem_in.data_ptr()
                 self._images_ptr = img.data_ptr()   # forward() points this at the caller's batch when it can be read in place
                 self.fwd_steps.append(lambda st, pin=pin, H=H, W=W: _C.check(
                     lib.rn_pack_image_nhwc4(self._images_ptr, B, H, W, self.stem_pad[0], self.stem_pad[1], self.Hp, self.Wp,
                                             pin, st), "rn_pack_image_nhwc4"))
-                live = self._conv_trainable(op)
-                p = _C.attach_splitk_workspace(_C.ConvProblem(), self.splitk_ws)
-                p.opts = self.launch_opts
-                p.R, p.S, p.stride_h, p.stride_w, p.pad_top, p.pad_left = self.stem_k, 1, 2, 2, 0, 0
-                p.act = _C.RN_ACT_NONE if live else _C.ACT_IDS[op["act"]]
-                p.out_dtype, p.num_segments = _C.RN_DT_BF16, 1
-                s = p.seg[0]
-                if live:
-                    s.x, s.w, s.y = pin, self.stem_packed.data_ptr(), self.raw[op["out"]].data_ptr()
-                    s.scale, s.shift, s.residual = None, None, None
-                else:
-                    sc, sh, _ = self.fold[op["out"]]
-                    s.x, s.w, s.y = pin, self.packed_frozen[op["conv"]].data_ptr(), y.data_ptr()
-                    s.scale, s.shift, s.residual = sc.data_ptr(), sh.data_ptr(), None
-                s.N, s.H, s.W, s.Cin, s.pix_stride = B, self.Hp, self.Wp, 32, 4
-                s.Ho, s.Wo, s.Cout = y.shape[1], y.shape[2], c["cout"]
-                self._keep.append(p)
-                if live:
+                if self._conv_trainable(op):
+                    p = stem_problem(self, self.raw[op["out"]], cout, self.stem_packed.data_ptr(), _C.RN_ACT_NONE)
+                    self._keep.append(p)
                     pb, sums, bsums, ws, dys = self._bn_problem([op])
                     self.bn_groups[op["out"]] = (pb, sums, bsums, ws, dys, [op])
                     prb = ctypes.byref(pb)
@@ -947,20 +816,18 @@ class TrainEngine:
                         self._bn_stats_finalize(prb, ws, sums, st)
                         self._bn_pass("bn_apply", pb, lambda: _C.check(lib.rn_bn_apply(prb, st), "rn_bn_apply"))
                     self.fwd_steps.append(run_stem)
+                    continue
+                sc, sh, _ = self.folded.fold[op["out"]]
+                p = stem_problem(self, y, cout, self.folded.packed[op["conv"]].data_ptr(), _C.ACT_IDS[op["act"]],
+                                 sc.data_ptr(), sh.data_ptr())
+                self._keep.append(p)
+                pool = stem_pool_partner(self.g, op, self.readers)
+                if pool is not None and not self.requires.get(op["out"]):
+                    # frozen stem (`resnet_initial`): conv + folded BatchNorm + relu + MaxPool in one launch
+                    self.fused_pools.add(pool["out"])
+                    self.fwd_steps.append(stem_pool_step(lib, p, pool, self.t[pool["out"]]))
                 else:
-                    from .engine import stem_pool_partner
-                    pool = stem_pool_partner(self.g, op, self.stem_k)
-                    if pool is not None and not self.requires.get(op["out"]):
-                        # frozen stem (`resnet_initial`): conv + folded BatchNorm + relu + MaxPool in one launch
-                        z = self.t[pool["out"]]
-                        fa = (pin, s.w, s.scale, s.shift, z.data_ptr(), B, self.Hp, self.Wp, y.shape[1], y.shape[2],
-                              self.stem_k, c["cout"], p.act, pool["k"], pool["stride"], pool["pad_top"], pool["pad_left"],
-                              z.shape[1], z.shape[2])
-                        self.fused_pools.add(pool["out"])
-                        self.fwd_steps.append(lambda st, fa=fa: _C.check(lib.rn_stem_conv_bn_relu_pool(*fa, st),
-                                                                         "rn_stem_conv_bn_relu_pool"))
-                    else:
-                        self.fwd_steps.append(lambda st, p=p: self._launch_conv(p, st, "stem"))
+                    self.fwd_steps.append(lambda st, p=p: self._launch_conv(p, st, "stem"))
             elif kind == "conv" and op["out"] in self._bneck_skip:
                 fb = self.bneck.get(op["out"])
                 if fb is not None:                 # the block's first op in graph order carries the launch
@@ -969,11 +836,8 @@ class TrainEngine:
                         if lprof is None:
                             fb.launch(st)
                             return
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        fb.launch(st)
-                        e1.record()
-                        lprof.append((e0, e1, "fwd:" + fb.name, fb.flops, fb.bytes, "bneck64_kernel (one launch per block)"))
+                        self._timed(lambda: fb.launch(st),
+                                    (lprof, ("fwd:" + fb.name, fb.flops, fb.bytes, "bneck64_kernel (one launch per block)")))
                     self.fwd_steps.append(run_block)
             elif kind == "conv":
                 grp = op.get("group")
@@ -1043,16 +907,9 @@ class TrainEngine:
             elif kind == "maxpool":
                 if op["out"] in self.fused_pools:   # written by the fused stem launch
                     continue
-                x, y = self.t[op["inp"]], self.t[op["out"]]
-                args = (x.data_ptr(), y.data_ptr(), B, x.shape[1], x.shape[2], x.shape[3], op["k"], op["stride"],
-                        op["pad_top"], op["pad_left"], y.shape[1], y.shape[2])
-                self.fwd_steps.append(lambda st, a=args: _C.check(lib.rn_maxpool2d_nhwc(*a, st), "maxpool"))
+                self.fwd_steps.append(maxpool_step(lib, op, self.t, B))
             elif kind == "topdown":
-                ins, outs = [self.t[n] for n in op["ins"]], [self.t[n] for n in op["outs"]]
-                pin, pout = _C.ptr_array(ins), _C.ptr_array(outs)
-                self._keep += [pin, pout]
-                a = (pin, pout, len(ins), B, ins[0].shape[1], ins[0].shape[2], ins[0].shape[3], _C.ACT_IDS[op["act"]])
-                self.fwd_steps.append(lambda st, a=a: _C.check(lib.rn_fpn_topdown(*a, st), "rn_fpn_topdown"))
+                self.fwd_steps.append(topdown_step(lib, op, self.t, B, self._keep))
             elif kind == "balance":
                 ts = [self.t[n] for n in op["tensors"]]
                 outs = [self.bal_out[n] for n in op["tensors"]]
@@ -1064,21 +921,7 @@ class TrainEngine:
                 a = (pin, pout, len(ts), op["mid"], B, ts[0].shape[1], ts[0].shape[2], ts[0].shape[3],
                      self.bal_avg.data_ptr())
                 self.fwd_steps.append(lambda st, a=a: _C.check(lib.rn_balance_features(*a, st), "rn_balance_features"))
-        # the tower convs were built before `balance` registered its outputs: rebuild is avoided by
-        # resolving inputs lazily — _conv_problem reads self.bal_src at build time, so build again
-        # for the groups that consume balanced tensors
-        if self.bal_src:
-            self._rebuild_consumers_of_balanced()
         self.outputs = {k: {lv: self.t[n] for lv, n in d.items()} for k, d in self.g.outputs.items()}
-
-    def _rebuild_consumers_of_balanced(self):
-        # the graph lists `balance` before the heads, so bal_src was already populated when the tower
-        # groups were built (ops are visited in order); nothing to do.  Kept as an assertion.
-        order = [o["op"] for o in self.ops]
-        bi = order.index("balance")
-        for o in self.ops[:bi]:
-            if o["op"] == "conv":
-                assert o["inp"] not in self.bal_src
 
     def _src(self, name):
         return self.bal_src.get(name, self.t[name])
@@ -1294,15 +1137,8 @@ class TrainEngine:
                     if prof is None and lprof is None:
                         _C.check(lib.rn_conv2d_nhwc_wgrad_group(*a, st), "rn_conv2d_nhwc_wgrad_group")
                         return
-                    cur = torch.cuda.current_stream(self.dev)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(cur)
-                    _C.check(lib.rn_conv2d_nhwc_wgrad_group(*a, st), "rn_conv2d_nhwc_wgrad_group")
-                    e1.record(cur)
-                    if prof is not None:
-                        prof.append((e0, e1, flw, wname))
-                    if lprof is not None:
-                        lprof.append((e0, e1, lname, flw, byw, wname))
+                    self._timed(lambda: _C.check(lib.rn_conv2d_nhwc_wgrad_group(*a, st), "rn_conv2d_nhwc_wgrad_group"),
+                                (prof, (flw, wname)), (lprof, (lname, flw, byw, wname)))
                 self._keep += [arr, dws, ws]
                 old_ws = {id(it[2]) for it in items}
                 self._keep = [k for k in self._keep if id(k) not in old_ws]      # the per-layer workspaces are not needed
@@ -1310,6 +1146,33 @@ class TrainEngine:
                 drop.update(grp[:-1])
                 self.wgrad_groups.append([it[0] for it in items])
         self.bwd_steps = [replace.get(i, fn) for i, fn in enumerate(self.bwd_steps) if i not in drop]
+
+    def _bn_bwd_step(self, pb, ws, bsums, ops):
+        """BatchNorm backward of the layers `ops` (problem pb): reduction -> SyncBN all-reduce of the sums -> apply (dy)"""
+        lib, prb = self.lib, ctypes.byref(pb)
+
+        def run(st):
+            self._bn_pass("bn_bwd_reduce", pb, lambda: _C.check(lib.rn_bn_bwd_reduce(prb, _C.ptr(ws), ws.numel(), st),
+                                                                 "rn_bn_bwd_reduce"))
+            if self.sync_bn:
+                self._allreduce_small(bsums)
+            self._bn_pass("bn_bwd_apply", pb, lambda: _C.check(lib.rn_bn_bwd_apply(prb, st), "rn_bn_bwd_apply"))
+        run.writes = [op["bn"] + sfx for op in ops for sfx in ("/gamma", "/beta")]
+        return run
+
+    @staticmethod
+    def _distinct_inputs(ops):
+        """the ops whose input needs a gradient, split into launches whose segments read distinct inputs (they write
+        distinct gradient buffers: both heads read the same pyramid level)"""
+        launches = []
+        for op in ops:
+            for sub in launches:
+                if all(o["inp"] != op["inp"] for o in sub):
+                    sub.append(op)
+                    break
+            else:
+                launches.append([op])
+        return launches
 
     def _plan_conv_backward(self, ops, mark):
         lib, B = self.lib, self.B
@@ -1328,17 +1191,8 @@ class TrainEngine:
                     res = op["residual"]
                     s.dres = self.grad[res].data_ptr()
                     s.dres_accumulate = 0 if mark(res) else 1
-            prb = ctypes.byref(pb)
             ws = self.bn_bwd_ws.get(id(pb), ws)   # stage 1 already written there by the dgrad launch that produced dz
-
-            def run(st, prb=prb, ws=ws, bsums=bsums, pb=pb):
-                self._bn_pass("bn_bwd_reduce", pb, lambda: _C.check(lib.rn_bn_bwd_reduce(prb, _C.ptr(ws), ws.numel(), st),
-                                                                     "rn_bn_bwd_reduce"))
-                if self.sync_bn:
-                    self._allreduce_small(bsums)
-                self._bn_pass("bn_bwd_apply", pb, lambda: _C.check(lib.rn_bn_bwd_apply(prb, st), "rn_bn_bwd_apply"))
-            run.writes = [op["bn"] + sfx for op in ops for sfx in ("/gamma", "/beta")]
-            self.bwd_steps.append(run)
+            self.bwd_steps.append(self._bn_bwd_step(pb, ws, bsums, ops))
             dy_of = {op["out"]: dys[i] for i, op in enumerate(ops)}
         else:
             dy_of = {}
@@ -1409,19 +1263,12 @@ class TrainEngine:
                     _C.check(lib.rn_conv2d_nhwc_wgrad(*a, st), "rn_conv2d_nhwc_wgrad")
                     return
                 # bench.py: HIP events on the stream the launch goes to (the side stream in the two-stream backward)
-                cur = torch.cuda.current_stream(self.dev)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(cur)
-                _C.check(lib.rn_conv2d_nhwc_wgrad(*a, st), "rn_conv2d_nhwc_wgrad")
-                e1.record(cur)
-                if prof is not None:
-                    prof.append((e0, e1, flw, wname))
-                if lprof is not None:
-                    lprof.append((e0, e1, lname, flw, byw, wname))
+                self._timed(lambda: _C.check(lib.rn_conv2d_nhwc_wgrad(*a, st), "rn_conv2d_nhwc_wgrad"),
+                            (prof, (flw, wname)), (lprof, (lname, flw, byw, wname)))
             step = self._side(wgrad, writes=[c.get("kvar", cname + "/kernel")])
             step.wgrad_item = (p, dw, ws, flw)      # _group_wgrad_steps may merge it with same-shape layers
             self.bwd_steps.append(step)
-            if c["bias"] and not (os.environ.get("RNET_DEBUG_SKIP_BIAS_GRAD") == "1"):   # (debug switch: timing probe only)
+            if c["bias"]:
                 # bias gradient = column sums of dy over every segment (two-stage reduction kernel)
                 pb2 = _C.BnProblem()
                 pb2.num_segments, pb2.act, pb2.bessel, pb2.eps, pb2.momentum, pb2.count_scale = len(cops), 0, 0, 0.0, 0.0, 1.0
@@ -1458,19 +1305,9 @@ class TrainEngine:
                     # sum of the per-level column sums (row 0 of every [2][cw] block), levels in order
                     _C.check(lib.rn_reduce_rows_f32(_C.ptr(bs), rows, stride, n, 0.0, _C.ptr(db), st), "bias grad")
                 self.bwd_steps.append(self._side(bias_grad, writes=[cname + "/bias"]))
-        # (c) data gradients.  Segments of one launch must write distinct gradient buffers (both
-        # heads read the same pyramid level): split the group into launches with unique inputs.
-        need = [op for op in ops if self.requires.get(op["inp"])]
-        launches = []
-        for op in need:
-            for sub in launches:
-                if all(o["inp"] != op["inp"] for o in sub):
-                    sub.append(op)
-                    break
-            else:
-                launches.append([op])
+        # (c) data gradients
         packs = {}
-        for sub in launches:
+        for sub in self._distinct_inputs([op for op in ops if self.requires.get(op["inp"])]):
             self._plan_dgrad_launch(sub, dy_of, mark, packs)
 
     def _plan_dw_backward(self, ops, mark):
@@ -1483,16 +1320,7 @@ class TrainEngine:
             pb, sums, bsums, ws, dys, _ = self.bn_groups[ops[0]["out"]]
             for i, op in enumerate(ops):
                 pb.seg[i].dz = self.grad[op["out"]].data_ptr()
-            prb = ctypes.byref(pb)
-
-            def run(st, prb=prb, ws=ws, bsums=bsums, pb=pb):
-                self._bn_pass("bn_bwd_reduce", pb, lambda: _C.check(lib.rn_bn_bwd_reduce(prb, _C.ptr(ws), ws.numel(), st),
-                                                                     "rn_bn_bwd_reduce"))
-                if self.sync_bn:
-                    self._allreduce_small(bsums)
-                self._bn_pass("bn_bwd_apply", pb, lambda: _C.check(lib.rn_bn_bwd_apply(prb, st), "rn_bn_bwd_apply"))
-            run.writes = [op["bn"] + sfx for op in ops for sfx in ("/gamma", "/beta")]
-            self.bwd_steps.append(run)
+            self.bwd_steps.append(self._bn_bwd_step(pb, ws, bsums, ops))
             dy_of = {op["out"]: dys[i] for i, op in enumerate(ops)}
         else:
             dy_of = {op["out"]: self.grad[op["out"]] for op in ops}
@@ -1516,17 +1344,8 @@ class TrainEngine:
             a = (ctypes.byref(p), self._pview(d["kvar"], self.G).data_ptr(), ws.data_ptr(), ws.numel())
             self.bwd_steps.append(self._side(lambda st, a=a: _C.check(lib.rn_depthwise_conv2d_nhwc_wgrad(*a, st),
                                                                      "dw wgrad"), writes=[d["kvar"]]))
-        need = [op for op in ops if self.requires.get(op["inp"])]
-        launches = []
-        for op in need:
-            for sub in launches:
-                if all(o["inp"] != op["inp"] for o in sub):
-                    sub.append(op)
-                    break
-            else:
-                launches.append([op])
         flips = {}
-        for sub in launches:
+        for sub in self._distinct_inputs([op for op in ops if self.requires.get(op["inp"])]):
             d0 = self.g.dws[sub[0]["dw"]]
             k, stride = d0["k"], d0["stride"]
             p = _C.DwProblem()
@@ -1568,26 +1387,11 @@ class TrainEngine:
                 _C.check(lib.rn_depthwise_conv2d_nhwc_fwd(ctypes.byref(p), st), "dw dgrad")
             self.bwd_steps.append(dgrad)
 
-    def _consumers(self, name):
-        """how many ops read tensor `name` (conv / depthwise / pooling inputs, residual inputs, top-down / balance
-        members)"""
-        if not hasattr(self, "_consumer_count"):
-            cnt = {}
-            for op in self.ops:
-                for key, val in op.items():
-                    if key in ("op", "out", "outs", "conv", "bn", "dw", "act", "group", "out_dtype", "kvar"):
-                        continue
-                    for v in (val if isinstance(val, (list, tuple)) else [val]):
-                        if isinstance(v, str) and v in self.tensors:
-                            cnt[v] = cnt.get(v, 0) + 1
-            self._consumer_count = cnt
-        return self._consumer_count.get(name, 0)
-
     def _bn_bwd_fusable(self, name):
         """(rn_bn_problem, segment) of the BatchNorm + ReLU layer that produced `name` when stage 1 of its backward
         reduction can run in the epilogue of the ONE data-gradient launch that writes its dz: trainable BatchNorm,
         relu, no residual input, no drop_connect factors, a single-segment group, a single consumer."""
-        if not self.fuse_bn_bwd or name in self.bal_src or self._consumers(name) != 1:
+        if not self.fuse_bn_bwd or name in self.bal_src or len(self.readers.get(name, [])) != 1:
             return None
         if not hasattr(self, "_bn_of_tensor"):
             self._bn_of_tensor = {}
@@ -1751,12 +1555,7 @@ class TrainEngine:
     # ---- one training step -----------------------------------------------------------------------------
     def refresh_dgrad_weights(self, st):
         lib = self.lib
-        if self.dgrad_packs and os.environ.get("RNET_BATCH_DGRAD_PACK", "1") == "0":   # A/B switch (tools/)
-            for (mptr, k, cin, cout, cw, buf, mode) in self.dgrad_packs:
-                if mode:
-                    raise RuntimeError("RNET_BATCH_DGRAD_PACK=0 has no sub-pixel packing: set RNET_DGRAD_SUBPIXEL=0 with it")
-                _C.check(lib.rn_pack_conv_weight_dgrad(mptr, k, k, cin, cout, cw, buf.data_ptr(), st), "pack dgrad")
-        elif self.dgrad_packs:
+        if self.dgrad_packs:
             if getattr(self, "_dgrad_pack_items", None) is None:   # descriptors are static: build them once
                 arr = (_C.DgradPack * len(self.dgrad_packs))()
                 for i, (mptr, k, cin, cout, cw, buf, mode) in enumerate(self.dgrad_packs):
@@ -2124,7 +1923,7 @@ class TrainEngine:
             optimistic = os.environ.get("RNET_C1_OPTIMISTIC_SGD", "1") != "0"
             applied = self._overlap_finish((lambda: sgd(self.G.data_ptr())) if optimistic else None)
             if applied:
-                self.refresh_stem_pack()
+                self.refresh_packs()
                 if self.loss_scale:
                     self._update_loss_scale()
                 return
@@ -2142,7 +1941,7 @@ class TrainEngine:
                 from retinanet.distribute import all_reduce_sum_bucketed
                 all_reduce_sum_bucketed(self.G, 2 if self.world == 1 else self.world, self.pg)   # executor.py:436-437: SUM after clipping
         sgd(skip)
-        self.refresh_stem_pack()
+        self.refresh_packs()
         if self.loss_scale:
             self._update_loss_scale()
 

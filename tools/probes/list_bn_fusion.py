@@ -13,4 +13,4 @@ fused = set(eng.bn_bwd_fused)
 for pb, _, _, _, _, gops in eng.bn_groups.values():
     for i, o in enumerate(gops):
         if o.get("act") == "relu" and not o.get("residual") and eng._bn_trainable(o):
-            print(o["out"], "fused" if o["out"] in fused else "NOT fused", "consumers", eng._consumers(o["out"]), "P", int(pb.seg[i].P), "C", int(pb.seg[i].C))
+            print(o["out"], "fused" if o["out"] in fused else "NOT fused", "consumers", len(eng.readers.get(o["out"], [])), "P", int(pb.seg[i].P), "C", int(pb.seg[i].C))
