@@ -25,8 +25,8 @@ max-pool has a gather-form backward.
 from __future__ import annotations
 
 import ctypes
-import math
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -47,6 +47,16 @@ def _hwio_to_ohwi(w):
 
 def _ohwi_to_hwio(w):
     return w.permute(1, 2, 3, 0).contiguous()
+
+
+class BnGroup(NamedTuple):
+    """The training-mode BatchNorm of one launch (TrainEngine.bn_groups, keyed by the first op's output)"""
+    problem: _C.BnProblem
+    sums: torch.Tensor     # [sum | sumsq] of every segment + the slot C2 rides in (the SyncBN forward message)
+    bsums: torch.Tensor    # [sum g | sum g*xhat] of every segment (the SyncBN backward message)
+    ws: torch.Tensor       # workspace of the two-stage reductions (partial sums, ticket counters)
+    dys: list              # per op: gradient at the conv output, written by rn_bn_bwd_apply
+    ops: list
 
 
 class TrainEngine:
@@ -74,6 +84,37 @@ class TrainEngine:
         self.params_cfg = model.params
         self.B = int(batch_size)
         self.dev = model.device
+        # ---- switches: every environment read of the engine, once.  (RNET_C1_OVERLAP alone is read at the head of every
+        # backward pass, _overlap_begin: bench.py and the data-parallel tests flip it on a live engine.)
+        env = os.environ.get
+        if force_dp is None:
+            force_dp = env("RNET_FORCE_DP", "0") == "1"
+        if wide_pred_terms is None:
+            wide_pred_terms = env("RNET_TRAIN_PRED_W_TERMS") or \
+                getattr(getattr(model.params, "training", None), "prediction_weight_planes", None) or 2
+        comm_cus = int(env("RNET_COMM_CUS", "8"))
+        self.fuse_bn_stats = env("RNET_FUSE_BN_STATS", "1") != "0"   # conv epilogue writes BN partial sums
+        # data-gradient epilogue writes stage 1 of the BatchNorm backward reduction of the layer it produces dz for
+        self.fuse_bn_bwd = env("RNET_FUSE_BN_BWD", "1") != "0"
+        # =2: also the multi-segment groups (the four head-tower depths).  Measured same-box: 3-4 more 122 us reduction
+        # launches go, the eight 550 us tower data gradients get ~15 us longer each in the step: +0.25 % on the step
+        # (round 3, with the weight-gradient CU cap: 31.06 -> 30.92 ms, +0.45 %, tools/probes/ab_env.sh) for -0.026 on the
+        # dominant kernel's MFMA fraction, the figure bench.py's roofline reports — off by default, the capability stays tested
+        self.fuse_bn_bwd_groups = env("RNET_FUSE_BN_BWD", "1") == "2"
+        # weight / bias gradient launches on a second HIP stream: nothing in the backward pass reads them, so they
+        # run beside the data-gradient chain (MFMA-bound wgrad next to the HBM-bound BatchNorm backward kernels)
+        self.side_stream_on = env("RNET_WGRAD_STREAM", "1") != "0"
+        cus = env("RNET_WGRAD_CUS", "160,208")   # round 6, same-box A/B (profiles/r06_ab/wgrad_cus.txt): 176,256 28.23, 160,208 28.01, 144,192 28.02, 112,192 30.3 ms
+        self._wgrad_cap = tuple(int(v) for v in cus.split(",")) if cus not in ("0", "") else None
+        if not self.side_stream_on:
+            self._wgrad_cap = None      # one-stream backward: nothing to leave CUs to
+        if self._wgrad_cap and len(self._wgrad_cap) == 1:
+            self._wgrad_cap = (self._wgrad_cap[0], 2 * self._wgrad_cap[0])
+        self._wgrad_group_mode = env("RNET_WGRAD_GROUP", "halo")   # "0" | "halo" | "all": see _group_wgrad_steps
+        self._ab_workspaces = env("RNET_AB_WORKSPACES") == "1"     # tools/ab_step.py switches kernel families between rounds
+        self._stream_probe = env("RNET_STREAM_PROBE", "1") != "0"  # _bucket_group_is_safe
+        self._bucket_bytes = int(env("RNET_C1_BUCKET_MB", "25")) << 20
+        # ---- configuration
         self.f16 = half_activations(model.params)    # (+ the LossScaleOptimizer arithmetic of optimizer_step)
         self.h16 = torch.float16 if self.f16 else torch.bfloat16
         self._DT = {"bf16": self.h16, "f32": torch.float32}
@@ -85,8 +126,6 @@ class TrainEngine:
         self.world = int(world_size)
         bn = self.params_cfg.architecture.batch_norm
         self.eps, self.momentum_bn = float(bn.epsilon), float(bn.momentum)
-        if force_dp is None:
-            force_dp = os.environ.get("RNET_FORCE_DP", "0") == "1"
         self.dp_active = self.world > 1 or bool(force_dp)    # collectives are issued (over 1 rank when forced)
         self.sync_bn = bool(bn.use_sync) and self.dp_active
         if isinstance(launch_opts, dict):
@@ -94,70 +133,79 @@ class TrainEngine:
         self.launch_opts = launch_opts.copy() if launch_opts is not None else _C.LaunchOpts()
         # data parallel: the persistent kernels leave a few CUs to RCCL (rn_launch_opts.reserved_cus)
         if self.dp_active and not self.launch_opts.reserved_cus:
-            self.launch_opts.reserved_cus = int(os.environ.get("RNET_COMM_CUS", "8"))
+            self.launch_opts.reserved_cus = comm_cus
         # the per-device handle (rn_create): device, CU count, this engine's launch defaults; owns the native communicators
         self.handle = _C.Handle(self.lib, self.dev.index if self.dev.index is not None else torch.cuda.current_device(),
                                 self.launch_opts)
-        if wide_pred_terms is None:
-            wide_pred_terms = os.environ.get("RNET_TRAIN_PRED_W_TERMS") or \
-                getattr(getattr(model.params, "training", None), "prediction_weight_planes", None) or 2
         self.wide_pred_terms = max(1, min(int(wide_pred_terms), _C.PRED_W_TERMS))
         self.frozen = set(frozen_names)
         for k in model.variables:
             if any(rx.search(k) for rx in frozen_regexes):
                 self.frozen.add(k)
+        # ---- what the build records
         self._keep = []
-        self._train_step_active = False
-        self._c2_local, self._c2_sent, self.c2_normalizer = None, False, None
-        self._overlap_on = False
-        self._overlap_done = 0
-        self._step_args = dict(wdc=0.0, alpha=0.0, unscale=1.0, clip=0.0)
-        self.native_comm = None   # retinanet.comm.NativeComm for the small per-layer messages (SyncBN, normaliser)
-        self.native_comm_buckets = None   # ... and a second one for the gradient buckets (rn_allreduce_bucket), or None
-        self._small_msgs = 0      # C3 messages (SyncBN sums; C2 rides in the first) sent since the step began
-        self.syncbn_messages_per_step = None   # their count in the last train_step (bench.py: config.syncbn_messages)
         self._algo = {}           # id(rn_conv_problem) -> (algorithmic FLOPs, algorithmic bytes) where the launch executes more
-        self.hbm_profile = None   # bench.py: list that collects (event0, event1, kernel name, algorithmic bytes)
         self.conv_launches = []   # (name, rn_conv_problem) of every implicit-GEMM launch: lib.rn_conv_kernel_id(byref(p))
+        self._launch_names = {}   # id(rn_conv_problem) -> that name (bench.py's layer_profile rows)
         self.wgrad_launches = []  # (name, rn_wgrad_problem) of every weight-gradient launch
         # (name, "fwd" | "dgrad", rn_dw_problem, rn_upsample_zero2x arguments run before it) of every depthwise launch
         self.dw_launches = []
         self.dw_wgrad_launches = []   # (name, rn_dw_problem) of every depthwise weight-gradient launch
         self.se_launches = []     # (name, "fwd" | "bwd", N, HW, C, se) of every squeeze-excite launch
-        cus = os.environ.get("RNET_WGRAD_CUS", "160,208")   # round 6, same-box A/B (profiles/r06_ab/wgrad_cus.txt): 176,256 28.23, 160,208 28.01, 144,192 28.02, 112,192 30.3 ms
-        self._wgrad_cap = tuple(int(v) for v in cus.split(",")) if cus not in ("0", "") else None
-        if os.environ.get("RNET_WGRAD_STREAM", "1") == "0":
-            self._wgrad_cap = None      # one-stream backward: nothing to leave CUs to
-        if self._wgrad_cap and len(self._wgrad_cap) == 1:
-            self._wgrad_cap = (self._wgrad_cap[0], 2 * self._wgrad_cap[0])
         self._wgrad_capped = []   # (problem, capped target): set_wgrad_cap(False) lifts the cap (bench.py's exclusive step)
-        self.step_count = 0
-        self.conv_profile = None
-        self.wgrad_profile = None   # bench.py: list that collects (event0, event1, algorithmic FLOPs, kernel) per wgrad launch
-        # bench.py `roofline.layers`: list that collects (event0, event1, launch name, algorithmic FLOPs, algorithmic bytes,
-        # kernel) for EVERY implicit-GEMM launch of the step — forward, data gradient, weight gradient
-        self.layer_profile = None
-        self.fuse_bn_stats = os.environ.get("RNET_FUSE_BN_STATS", "1") != "0"   # conv epilogue writes BN partial sums
-        # data-gradient epilogue writes stage 1 of the BatchNorm backward reduction of the layer it produces dz for
-        self.fuse_bn_bwd = os.environ.get("RNET_FUSE_BN_BWD", "1") != "0"
-        # =2: also the multi-segment groups (the four head-tower depths).  Measured same-box: 3-4 more 122 us reduction
-        # launches go, the eight 550 us tower data gradients get ~15 us longer each in the step: +0.25 % on the step
-        # (round 3, with the weight-gradient CU cap: 31.06 -> 30.92 ms, +0.45 %, tools/probes/ab_env.sh) for -0.026 on the
-        # dominant kernel's MFMA fraction, the figure bench.py's roofline reports — off by default, the capability stays tested
-        self.fuse_bn_bwd_groups = os.environ.get("RNET_FUSE_BN_BWD", "1") == "2"
-        self.bn_act_mask = os.environ.get("RNET_BN_ACT_MASK", "1") != "0"   # relu gates of the residual layers as bit masks
+        self.stem_packed = None   # live first-layer conv: its kernel as [Cout_pad][R rows][8 taps x 4 ch], repacked per step
+        self._bn_of_tensor = {}   # output of a live-BatchNorm layer -> (rn_bn_problem, segment, op, segments of the problem)
         self.bn_bwd_ws = {}       # id(rn_bn_problem) -> workspace that holds the externally written backward partials
-        self._bn_bwd_pending = {}  # id(rn_bn_problem) -> segments whose dz-writing launch is planned (see _plan_dgrad_launch)
+        self._bn_bwd_pending = {}  # id(rn_bn_problem) -> segments whose dz-writing launch is planned (see _fuse_bn_bwd)
         self.bn_bwd_fused = []    # tensor names whose BatchNorm backward reduction runs in a dgrad epilogue
-        # weight / bias gradient launches on a second HIP stream: nothing in the backward pass reads them, so they
-        # run beside the data-gradient chain (MFMA-bound wgrad next to the HBM-bound BatchNorm backward kernels)
-        self.side_stream_on = os.environ.get("RNET_WGRAD_STREAM", "1") != "0"
-        self._side_stream = None
+        self.dy_of = {}           # conv output -> gradient at the conv's own (pre-BatchNorm) output, what wgrad / dgrad read
+        self._loss_dy = None      # loss_grad_buffers(): the prediction convs' entries of dy_of
+        self._dgrad_pack_items = None   # rn_dgrad_pack array over dgrad_packs
         self.drop_connect = True     # stochastic depth of the EfficientNet skip blocks (efficientnet.py:97-113)
         self.dc_masks = {}           # project conv output -> (f32[B] factors, survival_prob)
         self.dc_all = self.dc_p = None
         self.dc_generator = torch.Generator(device=self.dev)
         self.dc_generator.manual_seed(1337)
+        # ---- state of the steps
+        self.step_count = 0
+        self.loss_scale = None    # LossScaleOptimizer state (mixed_float16 configs): see optimizer_step
+        self._ls_host = self._ls_event = None   # pinned copy of the "gradients not finite" flag and its event
+        self._ls_pending = False  # that copy has not been looked at yet (_resolve_loss_scale)
+        self._train_step_active = False
+        self._images_ref = None   # the caller's batch while forward() reads it in place
+        self._step_args = dict(wdc=0.0, alpha=0.0, unscale=1.0, clip=0.0)
+        self._side_stream = None
+        self._side_events = []
+        self.side_stream_probed = None
+        self._dgrad_prepacked = False   # train_step repacked the data-gradient weights beside the forward pass
+        self.conv_profile = None
+        self.wgrad_profile = None   # bench.py: list that collects (event0, event1, algorithmic FLOPs, kernel) per wgrad launch
+        # bench.py `roofline.layers`: list that collects (event0, event1, launch name, algorithmic FLOPs, algorithmic bytes,
+        # kernel) for EVERY implicit-GEMM launch of the step — forward, data gradient, weight gradient
+        self.layer_profile = None
+        self.hbm_profile = None   # bench.py: list that collects (event0, event1, kernel name, algorithmic bytes)
+        # ---- data parallel
+        self._c2_local, self._c2_sent, self.c2_normalizer = None, False, None
+        self.native_comm = None   # retinanet.comm.NativeComm for the small per-layer messages (SyncBN, normaliser)
+        self.native_comm_buckets = None   # ... and a second one for the gradient buckets (rn_allreduce_bucket), or None
+        self._small_msgs = 0      # C3 messages (SyncBN sums; C2 rides in the first) sent since the step began
+        self.syncbn_messages_per_step = None   # their count in the last train_step (bench.py: config.syncbn_messages)
+        self._overlap_on = False
+        self._overlap_done = 0
+        self._overlap_works = []
+        self._buckets = None      # the gradient buckets of the overlapped all-reduce, planned by the first pass that uses them
+        self._bucket_at = {}      # backward step -> buckets complete after it
+        self._comm_events = []    # per bucket: "the main stream's gradients of this bucket are enqueued"
+        self._bucket_stream = None   # the stream that carried the last pass's buckets
+        self._overlap_last_event = None   # recorded behind the last bucket launched
+        self.L = None             # what this rank contributed to the buckets (for the clip correction)
+        self.pg_c1 = None         # the buckets' own process group
+        self._probe_bucket_group = False   # pg_c1 is new: _bucket_group_is_safe has not looked at it yet
+        self._overlap_unsafe = False       # ... and found that its stream blocks the main stream: plain order
+        self._flag_host = self._flag_event = None   # pinned copy of the clip flag G[0] and its event
+        self.clip_fired = False
+        self.bucket_host_ms = 0.0
+        self.price_without_flag_read = False   # bench.py's extra.dp_overhead sets it: see _overlap_finish
         self._prepare_graph()
         with torch.cuda.device(self.dev):
             # split-K of the persistent conv kernels' last round (rn_conv_problem.splitk_ws): every forward / data-gradient
@@ -344,7 +392,10 @@ class TrainEngine:
         self._block_elems = [(segs[si][0] + (bi - segs[si][3]) * chunk, min(chunk, segs[si][1] - (bi - segs[si][3]) * chunk))
                              for bi, si in enumerate(block_seg)]   # (arena offset, elements) of every optimizer block
         self._seg_blocks = {k: (s[3], s[4]) for k, s in zip(names, segs)}   # variable -> (first block, blocks)
-        self.loss_scale = None     # LossScaleOptimizer state (mixed_float16 configs): see optimizer_step
+        stem = self._stem_op()
+        if self._conv_trainable(stem):
+            c = self.g.convs[stem["conv"]]
+            self.stem_packed = torch.zeros((lib.rn_conv_cout_pad(c["cout"]), c["k"], 32), dtype=self.h16, device=self.dev)
         self.load_from_model()
 
     def _pview(self, name, arena=None):
@@ -379,9 +430,6 @@ class TrainEngine:
         if self._conv_trainable(op):
             c = self.g.convs[op["conv"]]
             k = c["k"]
-            if getattr(self, "stem_packed", None) is None:
-                self.stem_packed = torch.zeros((self.lib.rn_conv_cout_pad(c["cout"]), k, 32), dtype=self.h16,
-                                               device=self.dev)
             w = _ohwi_to_hwio(self._pview(self._kvar(op)).reshape(c["cout"], k, k, 3))
             _C.check(self.lib.rn_pack_stem_weight_rs(_C.ptr(w), k, k, c["cout"], _C.ptr(self.stem_packed), st),
                      "rn_pack_stem_weight_rs")
@@ -608,8 +656,6 @@ class TrainEngine:
             if variant or lprof is not None:
                 lrow = None
                 if lprof is not None:
-                    if getattr(self, "_launch_names", None) is None or len(self._launch_names) != len(self.conv_launches):
-                        self._launch_names = {id(q): n for n, q in self.conv_launches}
                     kid = self.lib.rn_conv_kernel_id(ctypes.byref(p))
                     kname = variant or ("conv_fwd_kernel (128-row tiles)" if kid == 0 else f"kernel id {kid}")
                     lrow = (self._launch_names.get(id(p), what), flops, byts, kname)
@@ -704,23 +750,22 @@ class TrainEngine:
         """Batch statistics -> (mean, invstd, scale, shift) + moving statistics.  One replica: the final reduction
         kernel also finalizes; SyncBN: the [2][C] sums are all-reduced between the two."""
         lib = self.lib
-        if not self.sync_bn and os.environ.get("RNET_FUSE_BN_FINALIZE", "1") != "0":
+        if not self.sync_bn:
             _C.check(lib.rn_bn_stats_finalize(prb, _C.ptr(ws), ws.numel(), st), "rn_bn_stats_finalize")
             return
+        from retinanet.distribute import syncbn_merge
         _C.check(lib.rn_bn_stats(prb, _C.ptr(ws), ws.numel(), st), "rn_bn_stats")
-        if self.sync_bn:
-            from retinanet.distribute import syncbn_merge
-            # C2 (the loss normaliser's scalar all-reduce, retinanet_loss.py:46-49) rides in the spare slot of the step's
-            # FIRST SyncBN message instead of being a collective of its own
-            fold = self._c2_local is not None and not self._c2_sent
-            norm = syncbn_merge(sums, self.world, self._allreduce_small, self._c2_local if fold else None)
-            if fold:
-                self._c2_sent = True
-                self.c2_normalizer = norm
+        # C2 (the loss normaliser's scalar all-reduce, retinanet_loss.py:46-49) rides in the spare slot of the step's
+        # FIRST SyncBN message instead of being a collective of its own
+        fold = self._c2_local is not None and not self._c2_sent
+        norm = syncbn_merge(sums, self.world, self._allreduce_small, self._c2_local if fold else None)
+        if fold:
+            self._c2_sent = True
+            self.c2_normalizer = norm
         _C.check(lib.rn_bn_finalize(prb, st), "rn_bn_finalize")
 
     def _bn_problem(self, ops, conv_problem=None):
-        """BatchNorm problem over `ops`.  With `conv_problem` (the launch that produces the raw outputs): the forward
+        """BatchNorm problem over `ops` and its buffers (BnGroup).  With `conv_problem` (the launch that produces the raw outputs): the forward
         statistics' stage-1 partial sums are written by the conv epilogue (rn_conv_segment.bn_partial, one row per
         128 output pixels) and rn_bn_stats only does the final ordered reduction."""
         p = _C.BnProblem()
@@ -755,7 +800,7 @@ class TrainEngine:
             s.dgamma = self._pview(bn + "/gamma", self.G).data_ptr()
             s.dbeta = self._pview(bn + "/beta", self.G).data_ptr()
             s.P, s.C, s.dres_accumulate = y.shape[0] * y.shape[1] * y.shape[2], C, 0
-            if s.residual and op["act"] in ("relu", "relu6") and self.bn_act_mask:
+            if s.residual and op["act"] in ("relu", "relu6"):
                 # relu behind the residual add: the forward stores the gate as one bit per element, the two backward
                 # passes read P*C/8 bytes instead of z (rn_bn_segment.act_mask)
                 mk = torch.empty((int(s.P) * C // 8,), dtype=torch.uint8, device=self.dev)
@@ -783,14 +828,37 @@ class TrainEngine:
             for i in range(len(ops)):
                 conv_problem.seg[i].bn_partial = ws.data_ptr() + self.lib.rn_bn_partial_offset_bytes(ctypes.byref(p), i)
         self._keep += [p, sums, bsums, fwd, ws] + dys
-        return p, sums, bsums, ws, dys
+        return BnGroup(p, sums, bsums, ws, dys, ops)
 
     # ---- forward --------------------------------------------------------------------------------------
+    def _launch_ops(self, op, done):
+        """The ops of the launch that conv / depthwise `op` belongs to: the op itself, or its whole group when `op` is the
+        first of the group to turn up (`done`: the groups seen so far); [] when the group's launch was already built."""
+        grp = op.get("group")
+        if grp is None:
+            return [op]
+        if (op["op"], grp) in done:
+            return []
+        done.add((op["op"], grp))
+        return self._group_ops(op["op"], grp)
+
+    def _bn_train_step(self, launch, ops, conv_problem=None):
+        """Forward step of layers with a live BatchNorm: launch(st) writes the raw outputs -> batch statistics and
+        finalize -> rn_bn_apply (bracketed for bench.py's hbm_profile); registers the launch's BnGroup."""
+        grp = self.bn_groups[ops[0]["out"]] = self._bn_problem(ops, conv_problem)
+        lib, pb, prb = self.lib, grp.problem, ctypes.byref(grp.problem)
+
+        def run(st):
+            launch(st)
+            self._bn_stats_finalize(prb, grp.ws, grp.sums, st)
+            self._bn_pass("bn_apply", pb, lambda: _C.check(lib.rn_bn_apply(prb, st), "rn_bn_apply"))
+        return run
+
     def _build_forward(self):
         lib, B = self.lib, self.B
         self.fwd_steps = []
         self.fused_pools = set()   # MaxPool outputs written by rn_stem_conv_bn_relu_pool
-        self.bn_groups = {}   # first op out -> (problem, sums, bsums, ws, dys, ops)
+        self.bn_groups = {}   # first op out -> BnGroup
         self.bal_src = {}     # tensor name -> balance output tensor (consumers read the balanced copy)
         done = set()
         for op in self.ops:
@@ -807,15 +875,7 @@ class TrainEngine:
                 if self._conv_trainable(op):
                     p = stem_problem(self, self.raw[op["out"]], cout, self.stem_packed.data_ptr(), _C.RN_ACT_NONE)
                     self._keep.append(p)
-                    pb, sums, bsums, ws, dys = self._bn_problem([op])
-                    self.bn_groups[op["out"]] = (pb, sums, bsums, ws, dys, [op])
-                    prb = ctypes.byref(pb)
-
-                    def run_stem(st, p=p, prb=prb, ws=ws, sums=sums, pb=pb):
-                        self._launch_conv(p, st, "stem(train)")
-                        self._bn_stats_finalize(prb, ws, sums, st)
-                        self._bn_pass("bn_apply", pb, lambda: _C.check(lib.rn_bn_apply(prb, st), "rn_bn_apply"))
-                    self.fwd_steps.append(run_stem)
+                    self.fwd_steps.append(self._bn_train_step(lambda st, p=p: self._launch_conv(p, st, "stem(train)"), [op]))
                     continue
                 sc, sh, _ = self.folded.fold[op["out"]]
                 p = stem_problem(self, y, cout, self.folded.packed[op["conv"]].data_ptr(), _C.ACT_IDS[op["act"]],
@@ -840,55 +900,31 @@ class TrainEngine:
                                     (lprof, ("fwd:" + fb.name, fb.flops, fb.bytes, "bneck64_kernel (one launch per block)")))
                     self.fwd_steps.append(run_block)
             elif kind == "conv":
-                grp = op.get("group")
-                if grp is not None:
-                    if grp in done:
-                        continue
-                    done.add(grp)
-                    ops = self._group_ops("conv", grp)
-                else:
-                    ops = [op]
+                ops = self._launch_ops(op, done)
+                if not ops:
+                    continue
                 live_bn = bool(self._bn_trainable(ops[0]))
                 if any(bool(self._bn_trainable(o)) != live_bn for o in ops):
                     raise NotImplementedError("a conv group mixes frozen and live BatchNorm")
                 if live_bn:
                     pc = self._conv_problem(ops, lambda o: self.raw[o["out"]], raw_mode=True)
-                    pb, sums, bsums, ws, dys = self._bn_problem(ops, conv_problem=pc)
-                    self.bn_groups[ops[0]["out"]] = (pb, sums, bsums, ws, dys, ops)
-                    prb = ctypes.byref(pb)
-
-                    def run(st, pc=pc, prb=prb, ws=ws, sums=sums, pb=pb):
-                        self._launch_conv(pc, st, "conv(train)")
-                        self._bn_stats_finalize(prb, ws, sums, st)
-                        self._bn_pass("bn_apply", pb, lambda: _C.check(lib.rn_bn_apply(prb, st), "rn_bn_apply"))
-                    self.fwd_steps.append(run)
+                    self.fwd_steps.append(self._bn_train_step(lambda st, pc=pc: self._launch_conv(pc, st, "conv(train)"),
+                                                              ops, conv_problem=pc))
                 else:
                     for sub in split_by_depth(self.g, ops):
                         pc = self._conv_problem(sub, lambda o: self.t[o["out"]], raw_mode=False)
                         self.fwd_steps.append(lambda st, pc=pc: self._launch_conv(pc, st, "conv"))
             elif kind == "dwconv":
-                grp = op.get("group")
-                if grp is not None:
-                    if grp in done:
-                        continue
-                    done.add(grp)
-                    ops = [o for o in self.ops if o["op"] == "dwconv" and o.get("group") == grp]
-                else:
-                    ops = [op]
+                ops = self._launch_ops(op, done)
+                if not ops:
+                    continue
                 live_bn = bool(self._bn_trainable(ops[0]))
                 pd = self._dw_problem(ops, (lambda o: self.raw[o["out"]]) if live_bn else (lambda o: self.t[o["out"]]))
                 self.dw_launches.append(("dw:" + (ops[0].get("group") or ops[0]["out"]), "fwd", pd, []))
                 prd = ctypes.byref(pd)
                 if live_bn:
-                    pb, sums, bsums, ws, dys = self._bn_problem(ops)
-                    self.bn_groups[ops[0]["out"]] = (pb, sums, bsums, ws, dys, ops)
-                    prb = ctypes.byref(pb)
-
-                    def run_dw(st, prd=prd, prb=prb, ws=ws, sums=sums, pb=pb):
-                        _C.check(lib.rn_depthwise_conv2d_nhwc_fwd(prd, st), "depthwise(train)")
-                        self._bn_stats_finalize(prb, ws, sums, st)
-                        self._bn_pass("bn_apply", pb, lambda: _C.check(lib.rn_bn_apply(prb, st), "rn_bn_apply"))
-                    self.fwd_steps.append(run_dw)
+                    self.fwd_steps.append(self._bn_train_step(
+                        lambda st, prd=prd: _C.check(lib.rn_depthwise_conv2d_nhwc_fwd(prd, st), "depthwise(train)"), ops))
                 else:
                     if ops[0].get("act") not in (None, "none"):
                         raise NotImplementedError("depthwise conv with an activation but no BatchNorm")
@@ -922,37 +958,42 @@ class TrainEngine:
                      self.bal_avg.data_ptr())
                 self.fwd_steps.append(lambda st, a=a: _C.check(lib.rn_balance_features(*a, st), "rn_balance_features"))
         self.outputs = {k: {lv: self.t[n] for lv, n in d.items()} for k, d in self.g.outputs.items()}
+        self._bn_of_tensor = {o["out"]: (grp.problem, i, o, len(grp.ops))
+                              for grp in self.bn_groups.values() for i, o in enumerate(grp.ops)}
 
     def _src(self, name):
         return self.bal_src.get(name, self.t[name])
 
-    def _gradbuf(self, name):
-        return self.grad["bal:" + name] if name in self.bal_src else self.grad[name]
+    def _grad_target(self, name, mark, balanced=True):
+        """(gradient buffer of tensor `name`, True when the caller is its first writer in the backward order — `mark` is
+        _build_backward's record of that).  A reader of a balanced pyramid level read BalanceFeatures' copy, so its gradient
+        goes to the `bal:` buffer; balanced=False: the reader took the tensor itself (residual inputs)."""
+        key = "bal:" + name if balanced and name in self.bal_src else name
+        return self.grad[key], mark(key)
+
+    def _zero_upsampled(self, dy, H, W):
+        """dy of a stride-2 layer with zeros between its pixels, at the layer input's H x W: (buffer, the rn_upsample_zero2x
+        arguments that fill it).  The stride-1 form of the data gradient then runs on it."""
+        up = torch.empty((self.B, H, W, dy.shape[3]), dtype=self.h16, device=self.dev)
+        self._keep.append(up)
+        return up, (dy.data_ptr(), up.data_ptr(), self.B, dy.shape[1], dy.shape[2], dy.shape[3], H, W)
 
     # ---- backward ---------------------------------------------------------------------------------------
     def _build_backward(self):
         lib, B = self.lib, self.B
         self.bwd_steps = []
-        self.grad_init = {}       # tensor -> runtime flag "gradient buffer already written this step"
         self.dgrad_packs = []     # (master offset, conv dims, packed buffer)
         ops = self.ops
         self.dw_flip_packs = []   # (master offset, k, C, packed bf16 tap-reversed filter)
-        first_of_group, seen = {}, set()
-        for i, op in enumerate(ops):
-            if op["op"] in ("conv", "dwconv") and op.get("group") and (op["op"], op["group"]) not in seen:
-                seen.add((op["op"], op["group"]))
-                first_of_group[(op["op"], op["group"])] = i
-        plan = []
-        for i in range(len(ops) - 1, -1, -1):
-            op = ops[i]
+        plan, done = [], set()
+        for op in ops:     # the forward launches; a group stands where its first op does
             if op["op"] in ("conv", "dwconv"):
-                grp = op.get("group")
-                if grp is None:
-                    plan.append((op["op"], [op]))
-                elif first_of_group[(op["op"], grp)] == i:
-                    plan.append((op["op"], self._group_ops(op["op"], grp)))
+                launch = self._launch_ops(op, done)
+                if launch:
+                    plan.append((op["op"], launch))
             elif op["op"] in ("maxpool", "topdown", "balance", "stem", "se"):
                 plan.append((op["op"], op))
+        plan.reverse()
         # which tensor gradients get more than one contribution is decided at build time
         written = set()
 
@@ -995,33 +1036,31 @@ class TrainEngine:
                 op = item
                 if not self._conv_trainable(op):
                     continue
-                pb, sums, bsums, ws, dys, _ = self.bn_groups[op["out"]]
-                pb.seg[0].dz = self.grad[op["out"]].data_ptr()
+                grp = self.bn_groups[op["out"]]
+                grp.problem.seg[0].dz = self.grad[op["out"]].data_ptr()
+                dy = grp.dys[0]
                 c = self.g.convs[op["conv"]]
-                H, W = self.t["images"].shape[1], self.t["images"].shape[2]
                 pw = _C.WgradProblem()
                 pw.opts = self.launch_opts
                 k = self.stem_k
                 pw.R, pw.S, pw.stride_h, pw.stride_w, pw.pad_top, pw.pad_left, pw.num_segments = k, 1, 2, 2, 0, 0, 1
                 sg = pw.seg[0]
-                sg.x, sg.dy = self.stem_in.data_ptr(), dys[0].data_ptr()
-                sg.N, sg.H, sg.W, sg.Cin, sg.Ho, sg.Wo, sg.Cout = B, self.Hp, self.Wp, 32, dys[0].shape[1], dys[0].shape[2], c["cout"]
+                sg.x, sg.dy = self.stem_in.data_ptr(), dy.data_ptr()
+                sg.N, sg.H, sg.W, sg.Cin, sg.Ho, sg.Wo, sg.Cout = B, self.Hp, self.Wp, 32, dy.shape[1], dy.shape[2], c["cout"]
                 sg.x_pix_stride = 4
                 wsw = torch.empty((max(lib.rn_wgrad_workspace_bytes(ctypes.byref(pw)), 256),), dtype=torch.uint8,
                                   device=self.dev)
                 dwp = torch.zeros((c["cout"], k, 8, 4), dtype=torch.float32, device=self.dev)
                 gview = self._pview(self._kvar(op), self.G).view(c["cout"], k, k, 3)
                 self._keep += [pw, wsw, dwp]
+                bn_bwd = self._bn_bwd_step(grp, grp.ws, profiled=False)   # (its two passes were never rows of hbm_profile)
 
-                def stem_bwd(st, prb=ctypes.byref(pb), ws=ws, bsums=bsums, pw=pw, wsw=wsw, dwp=dwp, gview=gview, k=k):
-                    _C.check(lib.rn_bn_bwd_reduce(prb, _C.ptr(ws), ws.numel(), st), "rn_bn_bwd_reduce")
-                    if self.sync_bn:
-                        self._allreduce_small(bsums)
-                    _C.check(lib.rn_bn_bwd_apply(prb, st), "rn_bn_bwd_apply")
+                def stem_bwd(st, bn_bwd=bn_bwd, pw=pw, wsw=wsw, dwp=dwp, gview=gview, k=k):
+                    bn_bwd(st)
                     _C.check(lib.rn_conv2d_nhwc_wgrad(ctypes.byref(pw), dwp.data_ptr(), 0.0, wsw.data_ptr(),
                                                       wsw.numel(), st), "stem wgrad")
                     gview.copy_(dwp[:, :, :k, :3])   # [co][r][8 taps x 4 ch] -> [co][r][s][c]
-                stem_bwd.writes = [self._kvar(op), op["bn"] + "/gamma", op["bn"] + "/beta"]
+                stem_bwd.writes = [self._kvar(op)] + bn_bwd.writes
                 self.bwd_steps.append(stem_bwd)
             elif kind == "topdown":
                 op = item
@@ -1053,6 +1092,17 @@ class TrainEngine:
                 a = (pd, pi, pn, self.bal_avg.data_ptr(), scratch.data_ptr(), scratch.numel(), len(names), op["mid"], B,
                      ins[0].shape[1], ins[0].shape[2], ins[0].shape[3])
                 self.bwd_steps.append(lambda st, a=a: _C.check(lib.rn_balance_features_bwd(*a, st), "balance_bwd"))
+        # what the steps look up, static from here on
+        self._launch_names = {id(q): n for n, q in self.conv_launches}
+        # (a frozen prediction conv has no dy: such an engine serves forward() only)
+        self._loss_dy = {k: {lv: self.dy_of[name] for lv, name in self.g.outputs[k].items() if name in self.dy_of}
+                         for k in ("class-predictions", "box-predictions")}
+        if self.dgrad_packs:
+            arr = (_C.DgradPack * len(self.dgrad_packs))()
+            for i, (mptr, k, cin, cout, cw, buf, mode) in enumerate(self.dgrad_packs):
+                arr[i].w_ohwi, arr[i].w_packed = mptr, buf.data_ptr()
+                arr[i].R, arr[i].S, arr[i].Cin, arr[i].Cout, arr[i].Cout_pad, arr[i].pad_ = k, k, cin, cout, cw, mode
+            self._dgrad_pack_items = arr
 
     def set_wgrad_cap(self, on):
         """The CU cap of the weight-gradient launches (see _plan_conv_backward) on / off: with the chip to themselves
@@ -1069,6 +1119,42 @@ class TrainEngine:
             b += 2 * s.N * s.H * s.W * s.Cin + 2 * s.N * s.Ho * s.Wo * s.Cout
         return b + 4 * p.R * p.S * p.seg[0].Cin * p.seg[0].Cout
 
+    def _wgrad_kernel_name(self, p):
+        return ("wgrad_kernel (128x128 per-tap tiles)", "wgrad_big_kernel (256x256 per-tap tiles)",
+                "wgrad_halo_kernel")[max(self.lib.rn_wgrad_kernel_id(ctypes.byref(p)), 0)]
+
+    def _wgrad_workspace(self, problems, size):
+        """Split-K workspace of a weight-gradient launch over `problems`; size(): the library's byte count for their options
+        as they stand.  It must fit the capped plan, the uncapped one (set_wgrad_cap(False) lifts the cap on a live engine)
+        and, under RNET_AB_WORKSPACES=1, the other kernel families (tools/ab_step.py switches them between timed rounds)."""
+        def largest(field, values):
+            old = [getattr(p.opts, field) for p in problems]
+            n = 0
+            for v in values:
+                for p in problems:
+                    setattr(p.opts, field, v)
+                n = max(n, size())
+            for p, v in zip(problems, old):
+                setattr(p.opts, field, v)
+            return n
+        nws = size()
+        if any(p.opts.wgrad_target_blocks for p in problems):
+            nws = max(nws, largest("wgrad_target_blocks", (0,)))
+        if self._ab_workspaces:
+            nws = max(nws, largest("wgrad_kernel", (1, 3)))
+        return torch.empty((max(nws, 256),), dtype=torch.uint8, device=self.dev)
+
+    def _wgrad_step(self, call, args, what, flops, byts, kname, lname, writes):
+        """Side-stream step of one weight-gradient library call `call(*args, stream)`, bracketed with events on the stream
+        it goes to (the side stream in the two-stream backward) while bench.py collects wgrad_profile / layer_profile."""
+        def wgrad(st):
+            prof, lprof = self.wgrad_profile, self.layer_profile
+            if prof is None and lprof is None:
+                _C.check(call(*args, st), what)
+                return
+            self._timed(lambda: _C.check(call(*args, st), what), (prof, (flops, kname)), (lprof, (lname, flops, byts, kname)))
+        return self._side(wgrad, writes=writes)
+
     def _group_wgrad_steps(self):
         """Weight-gradient launches of layers with IDENTICAL geometry become one rn_conv2d_nhwc_wgrad_group call (the
         eight head-tower layers, the 3x3 layers of a ResNet stage: up to 8 per call), issued where the LAST of them
@@ -1078,7 +1164,7 @@ class TrainEngine:
         tile, ~75 MB per launch however small the layer.  RNET_WGRAD_GROUP=0 keeps one launch per layer."""
         lib = self.lib
         self.wgrad_groups = []
-        if os.environ.get("RNET_WGRAD_GROUP", "1") == "0":
+        if self._wgrad_group_mode == "0":
             return
         by_sig = {}
         for i, fn in enumerate(self.bwd_steps):
@@ -1097,7 +1183,8 @@ class TrainEngine:
                 if len(grp) < 2:
                     continue
                 items = [self.bwd_steps[i].wgrad_item for i in grp]
-                arr = (ctypes.POINTER(_C.WgradProblem) * len(grp))(*[ctypes.pointer(it[0]) for it in items])
+                probs = [it[0] for it in items]
+                arr = (ctypes.POINTER(_C.WgradProblem) * len(grp))(*[ctypes.pointer(p) for p in probs])
                 if lib.rn_wgrad_group_fused(arr, len(grp)) != 1:
                     continue
                 # Groups the halo kernel does not serve — the 1x1 layers of a ResNet stage, five / six of one geometry, which
@@ -1106,58 +1193,37 @@ class TrainEngine:
                 # grouped against 28.10 / 28.14 / 28.22 ms per step.  A group is issued where its LAST layer stood, which
                 # moves ~40 small launches' work to the end of the weight-gradient stream — the stream that already ends
                 # 0.5 ms after the main one.  RNET_WGRAD_GROUP=all groups them (the library path stays tested).
-                if os.environ.get("RNET_WGRAD_GROUP", "halo") != "all" and \
-                        lib.rn_wgrad_kernel_id(ctypes.byref(items[0][0])) != 2:
+                if self._wgrad_group_mode != "all" and lib.rn_wgrad_kernel_id(ctypes.byref(probs[0])) != 2:
                     continue
-                nws = lib.rn_wgrad_group_workspace_bytes(arr, len(grp))
-                caps = [int(it[0].opts.wgrad_target_blocks) for it in items]
-                if any(caps):          # the uncapped plan (set_wgrad_cap(False)) must fit too
-                    for it in items:
-                        it[0].opts.wgrad_target_blocks = 0
-                    nws = max(nws, lib.rn_wgrad_group_workspace_bytes(arr, len(grp)))
-                    for it, c in zip(items, caps):
-                        it[0].opts.wgrad_target_blocks = c
-                if os.environ.get("RNET_AB_WORKSPACES") == "1":   # tools/ab_step.py switches kernel families between rounds
-                    nws = max([nws] + [int(it[2].numel()) for it in items])
-                ws = torch.empty((max(nws, 256),), dtype=torch.uint8, device=self.dev)
+                ws = self._wgrad_workspace(probs, lambda: lib.rn_wgrad_group_workspace_bytes(arr, len(grp)))
                 dws = _C.ptr_array([it[1] for it in items])
-                flw = sum(it[3] for it in items)
-                writes = [w for i in grp for w in self.bwd_steps[i].writes]
-                a = (arr, len(grp), dws, 0.0, ws.data_ptr(), ws.numel())
-                kname = ("wgrad_kernel (128x128 per-tap tiles)", "wgrad_big_kernel (256x256 per-tap tiles)",
-                         "wgrad_halo_kernel")[max(lib.rn_wgrad_kernel_id(ctypes.byref(items[0][0])), 0)]
-                wname = f"{kname} ({len(grp)} layers per launch) + wgrad_reduce_kernel"
-
-                byw = sum(self._wgrad_bytes(it[0]) for it in items)
+                wname = f"{self._wgrad_kernel_name(probs[0])} ({len(grp)} layers per launch) + wgrad_reduce_kernel"
                 lname = "wgrad:" + "+".join(n[len("wgrad:"):] for n, q in self.wgrad_launches
-                                            if any(q is it[0] for it in items))
-
-                def wgrad_group(st, a=a, flw=flw, wname=wname, byw=byw, lname=lname):
-                    prof, lprof = self.wgrad_profile, self.layer_profile
-                    if prof is None and lprof is None:
-                        _C.check(lib.rn_conv2d_nhwc_wgrad_group(*a, st), "rn_conv2d_nhwc_wgrad_group")
-                        return
-                    self._timed(lambda: _C.check(lib.rn_conv2d_nhwc_wgrad_group(*a, st), "rn_conv2d_nhwc_wgrad_group"),
-                                (prof, (flw, wname)), (lprof, (lname, flw, byw, wname)))
+                                            if any(q is p for p in probs))
                 self._keep += [arr, dws, ws]
                 old_ws = {id(it[2]) for it in items}
                 self._keep = [k for k in self._keep if id(k) not in old_ws]      # the per-layer workspaces are not needed
-                replace[grp[-1]] = self._side(wgrad_group, writes=writes)
+                replace[grp[-1]] = self._wgrad_step(
+                    lib.rn_conv2d_nhwc_wgrad_group, (arr, len(grp), dws, 0.0, ws.data_ptr(), ws.numel()),
+                    "rn_conv2d_nhwc_wgrad_group", sum(it[3] for it in items), sum(self._wgrad_bytes(p) for p in probs),
+                    wname, lname, [w for i in grp for w in self.bwd_steps[i].writes])
                 drop.update(grp[:-1])
-                self.wgrad_groups.append([it[0] for it in items])
+                self.wgrad_groups.append(probs)
         self.bwd_steps = [replace.get(i, fn) for i, fn in enumerate(self.bwd_steps) if i not in drop]
 
-    def _bn_bwd_step(self, pb, ws, bsums, ops):
-        """BatchNorm backward of the layers `ops` (problem pb): reduction -> SyncBN all-reduce of the sums -> apply (dy)"""
-        lib, prb = self.lib, ctypes.byref(pb)
+    def _bn_bwd_step(self, grp, ws, profiled=True):
+        """BatchNorm backward of the layers of BnGroup `grp`: reduction (over the partials in `ws`) -> SyncBN all-reduce
+        of the sums -> apply (dy).  profiled=False keeps the two passes out of bench.py's hbm_profile."""
+        lib, pb, prb, bsums = self.lib, grp.problem, ctypes.byref(grp.problem), grp.bsums
+        bracket = self._bn_pass if profiled else (lambda kind, pb, fn: fn())
 
         def run(st):
-            self._bn_pass("bn_bwd_reduce", pb, lambda: _C.check(lib.rn_bn_bwd_reduce(prb, _C.ptr(ws), ws.numel(), st),
-                                                                 "rn_bn_bwd_reduce"))
+            bracket("bn_bwd_reduce", pb, lambda: _C.check(lib.rn_bn_bwd_reduce(prb, _C.ptr(ws), ws.numel(), st),
+                                                           "rn_bn_bwd_reduce"))
             if self.sync_bn:
                 self._allreduce_small(bsums)
-            self._bn_pass("bn_bwd_apply", pb, lambda: _C.check(lib.rn_bn_bwd_apply(prb, st), "rn_bn_bwd_apply"))
-        run.writes = [op["bn"] + sfx for op in ops for sfx in ("/gamma", "/beta")]
+            bracket("bn_bwd_apply", pb, lambda: _C.check(lib.rn_bn_bwd_apply(prb, st), "rn_bn_bwd_apply"))
+        run.writes = [op["bn"] + sfx for op in grp.ops for sfx in ("/gamma", "/beta")]
         return run
 
     @staticmethod
@@ -1183,17 +1249,17 @@ class TrainEngine:
         live_bn = bool(self._bn_trainable(ops[0]))
         # (a) gradient wrt the conv output
         if live_bn:
-            pb, sums, bsums, ws, dys, _ = self.bn_groups[ops[0]["out"]]
+            grp = self.bn_groups[ops[0]["out"]]
+            pb = grp.problem
             for i, op in enumerate(ops):
                 s = pb.seg[i]
                 s.dz = self.grad[op["out"]].data_ptr()
                 if op.get("residual") and self.requires.get(op["residual"]):
-                    res = op["residual"]
-                    s.dres = self.grad[res].data_ptr()
-                    s.dres_accumulate = 0 if mark(res) else 1
-            ws = self.bn_bwd_ws.get(id(pb), ws)   # stage 1 already written there by the dgrad launch that produced dz
-            self.bwd_steps.append(self._bn_bwd_step(pb, ws, bsums, ops))
-            dy_of = {op["out"]: dys[i] for i, op in enumerate(ops)}
+                    dres, first = self._grad_target(op["residual"], mark, balanced=False)
+                    s.dres, s.dres_accumulate = dres.data_ptr(), 0 if first else 1
+            # (ws: stage 1 already written there by the dgrad launch that produced dz)
+            self.bwd_steps.append(self._bn_bwd_step(grp, self.bn_bwd_ws.get(id(pb), grp.ws)))
+            dy_of = {op["out"]: grp.dys[i] for i, op in enumerate(ops)}
         else:
             dy_of = {}
             for op in ops:
@@ -1209,7 +1275,6 @@ class TrainEngine:
                          dyb.numel(), _C.ACT_IDS[op["act"]])
                     self.bwd_steps.append(lambda st, a=a: _C.check(lib.rn_act_bwd(*a, st), "rn_act_bwd"))
             self._keep += list(dy_of.values())
-        self.dy_of = getattr(self, "dy_of", {})
         self.dy_of.update(dy_of)
         # (b) weight / bias gradients, one problem per distinct (shared) conv layer
         by_conv = {}
@@ -1217,6 +1282,7 @@ class TrainEngine:
             by_conv.setdefault(op["conv"], []).append(op)
         for cname, cops in by_conv.items():
             c = self.g.convs[cname]
+            kvar = c.get("kvar", cname + "/kernel")
             p = _C.WgradProblem()
             p.opts = self.launch_opts
             p.R = p.S = c["k"]
@@ -1229,7 +1295,6 @@ class TrainEngine:
                 s.x, s.dy = x.data_ptr(), dy.data_ptr()
                 s.N, s.H, s.W, s.Cin, s.Ho, s.Wo, s.Cout = B, x.shape[1], x.shape[2], c["cin"], dy.shape[1], dy.shape[2], c["cout"]
                 s.dy_pix_stride = dy.shape[3]
-            nws = lib.rn_wgrad_workspace_bytes(ctypes.byref(p))
             # Two-stream backward: a weight-gradient launch is capped to ~2/3 of the CUs (rn_launch_opts.wgrad_target_blocks).
             # Its persistent workgroups own a CU for hundreds of microseconds; when they cover the whole chip every
             # main-stream launch — the critical path — queues behind them.  Measured in one process (tools/ab_step.py):
@@ -1238,34 +1303,16 @@ class TrainEngine:
             if self._wgrad_cap and not p.opts.wgrad_target_blocks:
                 kid = lib.rn_wgrad_kernel_id(ctypes.byref(p))
                 p.opts.wgrad_target_blocks = self._wgrad_cap[0] if kid in (1, 2) else self._wgrad_cap[1]
-                nws = max(nws, lib.rn_wgrad_workspace_bytes(ctypes.byref(p)))   # either plan fits: set_wgrad_cap() may lift it
                 self._wgrad_capped.append((p, int(p.opts.wgrad_target_blocks)))
-            if os.environ.get("RNET_AB_WORKSPACES") == "1":   # tools/ab_step.py switches kernel families between timed rounds
-                for alt in (1, 3):
-                    q = _C.WgradProblem.from_buffer_copy(p)
-                    q.opts.wgrad_kernel = alt
-                    nws = max(nws, lib.rn_wgrad_workspace_bytes(ctypes.byref(q)))
-            ws = torch.empty((max(nws, 256),), dtype=torch.uint8, device=self.dev)
-            dw = self._pview(c.get("kvar", cname + "/kernel"), self.G)
+            ws = self._wgrad_workspace([p], lambda: lib.rn_wgrad_workspace_bytes(ctypes.byref(p)))
+            dw = self._pview(kvar, self.G)
             self._keep += [p, ws]
             self.wgrad_launches.append(("wgrad:" + cname, p))
-            a = (ctypes.byref(p), dw.data_ptr(), 0.0, ws.data_ptr(), ws.numel())
             # algorithmic FLOPs of the layer's weight gradient: 2 * pixels * k*k * Cin * Cout over the segments
             flw = sum(2 * B * p.seg[i].Ho * p.seg[i].Wo * c["k"] * c["k"] * c["cin"] * c["cout"] for i in range(len(cops)))
-            wname = ("wgrad_kernel (128x128 per-tap tiles)", "wgrad_big_kernel (256x256 per-tap tiles)",
-                     "wgrad_halo_kernel")[max(lib.rn_wgrad_kernel_id(ctypes.byref(p)), 0)] + " + wgrad_reduce_kernel"
-
-            byw = self._wgrad_bytes(p)
-
-            def wgrad(st, a=a, flw=flw, wname=wname, byw=byw, lname="wgrad:" + cname):
-                prof, lprof = self.wgrad_profile, self.layer_profile
-                if prof is None and lprof is None:
-                    _C.check(lib.rn_conv2d_nhwc_wgrad(*a, st), "rn_conv2d_nhwc_wgrad")
-                    return
-                # bench.py: HIP events on the stream the launch goes to (the side stream in the two-stream backward)
-                self._timed(lambda: _C.check(lib.rn_conv2d_nhwc_wgrad(*a, st), "rn_conv2d_nhwc_wgrad"),
-                            (prof, (flw, wname)), (lprof, (lname, flw, byw, wname)))
-            step = self._side(wgrad, writes=[c.get("kvar", cname + "/kernel")])
+            step = self._wgrad_step(lib.rn_conv2d_nhwc_wgrad, (ctypes.byref(p), dw.data_ptr(), 0.0, ws.data_ptr(), ws.numel()),
+                                    "rn_conv2d_nhwc_wgrad", flw, self._wgrad_bytes(p),
+                                    self._wgrad_kernel_name(p) + " + wgrad_reduce_kernel", "wgrad:" + cname, [kvar])
             step.wgrad_item = (p, dw, ws, flw)      # _group_wgrad_steps may merge it with same-shape layers
             self.bwd_steps.append(step)
             if c["bias"]:
@@ -1282,10 +1329,10 @@ class TrainEngine:
                 # A conv in front of a live BatchNorm: its dy is written by rn_bn_bwd_apply, which can sum the columns of
                 # what it stores on the way out (rn_bn_segment.dy_colsum_partial) — stage 1 of this reduction then never
                 # reads the dy tensor again (FPN + head-tower convs: 17 launches, ~1 ms of side-stream HBM reads per step;
-                # same-process A/B of the step with / without ANY bias-gradient launch: 29.73 / 29.50 ms).
-                # RNET_FUSE_BIAS_GRAD=0 keeps the separate pass.
+                # same-process A/B of the step with / without ANY bias-gradient launch: 29.73 / 29.50 ms).  Where
+                # rn_bn_bwd_colsum_chunks refuses a segment the separate pass stays.
                 fused_cs = False
-                if live_bn and os.environ.get("RNET_FUSE_BIAS_GRAD", "1") != "0":
+                if live_bn:
                     seg_of = [ops.index(op) for op in cops]
                     chunks = [lib.rn_bn_bwd_colsum_chunks(ctypes.byref(pb), j) for j in seg_of]
                     if all(ch > 0 for ch in chunks):
@@ -1315,13 +1362,12 @@ class TrainEngine:
         shared separable conv); data gradient = the forward kernel on (zero-upsampled) dy with the
         tap-reversed filter, accumulating into gradient buffers that already hold a contribution."""
         lib, B = self.lib, self.B
-        live_bn = bool(self._bn_trainable(ops[0]))
-        if live_bn:
-            pb, sums, bsums, ws, dys, _ = self.bn_groups[ops[0]["out"]]
+        if self._bn_trainable(ops[0]):
+            grp = self.bn_groups[ops[0]["out"]]
             for i, op in enumerate(ops):
-                pb.seg[i].dz = self.grad[op["out"]].data_ptr()
-            self.bwd_steps.append(self._bn_bwd_step(pb, ws, bsums, ops))
-            dy_of = {op["out"]: dys[i] for i, op in enumerate(ops)}
+                grp.problem.seg[i].dz = self.grad[op["out"]].data_ptr()
+            self.bwd_steps.append(self._bn_bwd_step(grp, grp.ws))
+            dy_of = {op["out"]: grp.dys[i] for i, op in enumerate(ops)}
         else:
             dy_of = {op["out"]: self.grad[op["out"]] for op in ops}
         by_layer = {}
@@ -1348,6 +1394,8 @@ class TrainEngine:
         for sub in self._distinct_inputs([op for op in ops if self.requires.get(op["inp"])]):
             d0 = self.g.dws[sub[0]["dw"]]
             k, stride = d0["k"], d0["stride"]
+            if stride not in (1, 2):
+                raise NotImplementedError("stride > 2")
             p = _C.DwProblem()
             p.k, p.stride, p.act, p.num_segments = k, 1, 0, len(sub)
             p.pad_top, p.pad_left = k - 1 - sub[0]["pad_top"], k - 1 - sub[0]["pad_left"]
@@ -1359,20 +1407,13 @@ class TrainEngine:
                     flips[op["dw"]] = buf
                     off, _ = self.p_off[d["kvar"]]
                     self.dw_flip_packs.append((self.P.data_ptr() + 4 * off, k, d["C"], buf))
-                dy = dy_of[op["out"]]
+                src = dy_of[op["out"]]
                 x = self._src(op["inp"])
                 H, W = x.shape[1], x.shape[2]
                 if stride == 2:
-                    up = torch.empty((B, H, W, d["C"]), dtype=self.h16, device=self.dev)
-                    ups.append((dy.data_ptr(), up.data_ptr(), B, dy.shape[1], dy.shape[2], d["C"], H, W))
-                    self._keep.append(up)
-                    src = up
-                elif stride == 1:
-                    src = dy
-                else:
-                    raise NotImplementedError("stride > 2")
-                gbuf = self._gradbuf(op["inp"])
-                first = mark(op["inp"] if op["inp"] not in self.bal_src else "bal:" + op["inp"])
+                    src, up_args = self._zero_upsampled(src, H, W)
+                    ups.append(up_args)
+                gbuf, first = self._grad_target(op["inp"], mark)
                 s = p.seg[i]
                 s.x, s.w, s.y = src.data_ptr(), flips[op["dw"]].data_ptr(), gbuf.data_ptr()
                 s.scale, s.shift = None, None
@@ -1393,11 +1434,6 @@ class TrainEngine:
         relu, no residual input, no drop_connect factors, a single-segment group, a single consumer."""
         if not self.fuse_bn_bwd or name in self.bal_src or len(self.readers.get(name, [])) != 1:
             return None
-        if not hasattr(self, "_bn_of_tensor"):
-            self._bn_of_tensor = {}
-            for pb, _, _, _, _, gops in self.bn_groups.values():
-                for i, o in enumerate(gops):
-                    self._bn_of_tensor[o["out"]] = (pb, i, o, len(gops))
         hit = self._bn_of_tensor.get(name)
         if hit is None:
             return None
@@ -1409,159 +1445,136 @@ class TrainEngine:
             return None
         return pb, i
 
+    def _fuse_bn_bwd(self, p, need):
+        """Stage 1 of the BatchNorm backward reduction of the layers whose dz the data-gradient launch `p` over `need`
+        writes, in its epilogue.  Returns the algorithmic bytes this adds to `p` (the y its epilogue reads).
+        All segments of a BatchNorm problem or none (rn_bn_bwd_reduce): a problem is switched over once the launches
+        planned so far write dz of EVERY one of its segments, each exactly once — one launch for a bottleneck layer,
+        one launch over both heads x five levels for head-tower depths 0-2, the two prediction convs' data gradients
+        together for depth 3.  Until then the assignments wait in self._bn_bwd_pending; the rn_conv_problem structs
+        are read at launch time, so they can still be patched when the last segment turns up."""
+        lib = self.lib
+        hits = [self._bn_bwd_fusable(op["inp"]) for op in need]
+        if any(h is None for h in hits):
+            return 0
+        added = 0
+        for i, (op, (pb, j)) in enumerate(zip(need, hits)):
+            pend = self._bn_bwd_pending.setdefault(id(pb), {"pb": pb, "seg": {}})
+            if j in pend["seg"]:          # a second writer: not a single-consumer layer after all
+                pend["dead"] = True
+            pend["seg"][j] = (p, i, op["inp"])
+        for key in {id(pb) for pb, _ in hits}:
+            pend = self._bn_bwd_pending[key]
+            pb = pend["pb"]
+            if pend.get("dead") or pend.get("done") or sorted(pend["seg"]) != list(range(pb.num_segments)):
+                continue
+            pend["done"] = True
+            for j, (cp, ci, _) in pend["seg"].items():
+                pb.seg[j].ext_chunks_bwd = lib.rn_conv_bn_row_blocks(ctypes.byref(cp), ci)
+            wsb = torch.zeros((max(lib.rn_bn_workspace_bytes(ctypes.byref(pb)), 256),), dtype=torch.uint8, device=self.dev)
+            self.bn_bwd_ws[key] = wsb
+            for j, (cp, ci, name) in pend["seg"].items():
+                sg = cp.seg[ci]
+                sg.bn_partial = wsb.data_ptr() + lib.rn_bn_bwd_partial_offset_bytes(ctypes.byref(pb), j)
+                sg.bn_bwd_y = self.raw[name].data_ptr()
+                sg.bn_bwd_fwd = pb.seg[j].fwd
+                self.bn_bwd_fused.append(name)
+                y_bytes = 2 * int(pb.seg[j].P) * int(pb.seg[j].C)
+                if cp is p:
+                    added += y_bytes
+                else:                      # an earlier launch: add the bytes of y its epilogue now reads
+                    fl0, by0 = self._algo[id(cp)]
+                    self._algo[id(cp)] = (fl0, by0 + y_bytes)
+        return added
+
     def _plan_dgrad_launch(self, need, dy_of, mark, packs):
+        """One data-gradient launch over the ops `need` (distinct inputs): the forward implicit-GEMM kernel on dy with the
+        flipped / transposed weights, in one of three forms chosen per launch."""
         lib, B = self.lib, self.B
         c0 = self.g.convs[need[0]["conv"]]
-        k, stride = c0["k"], c0["stride"]
-        p = _C.attach_splitk_workspace(_C.ConvProblem(), self.splitk_ws)
-        p.opts = self.launch_opts
-        p.R = p.S = k
-        p.stride_h = p.stride_w = 1
-        p.pad_top = p.pad_left = k - 1 - need[0]["pad"]
-        p.act, p.out_dtype, p.num_segments = _C.RN_ACT_NONE, _C.RN_DT_BF16, len(need)
-        ups = []
+        k, stride, pad = c0["k"], c0["stride"], need[0]["pad"]
+        if stride not in (1, 2):
+            raise NotImplementedError("stride > 2")
         # 1x1 / stride 2 (projection shortcuts): dx is non-zero only at the even positions, so the GEMM runs on dy
         # as it is (a quarter of the pixels of the zero-upsampled form) and rn_scatter_add2x puts the rows in place
-        lowres = k == 1 and stride == 2 and need[0]["pad"] == 0 and os.environ.get("RNET_DGRAD_LOWRES", "1") != "0"
-        scatters = []
+        lowres = k == 1 and stride == 2 and pad == 0
         # 3x3 / stride 2 / pad 1 on even inputs (the first block of ResNet stages 2-4): sub-pixel form — one 2x2
         # stride-1 conv of dy with 4*Cin phase-major output channels + a depth-to-space, 16 tap products per dy pixel
         # instead of the 36 (9 useful) of the zero-upsampled form (rn_dgrad_pack.pad_ == 1)
-        subpixel = (k == 3 and stride == 2 and need[0]["pad"] == 1 and os.environ.get("RNET_DGRAD_SUBPIXEL", "1") != "0"
+        subpixel = (k == 3 and stride == 2 and pad == 1
                     and all(self._src(o["inp"]).shape[1] % 2 == 0 and self._src(o["inp"]).shape[2] % 2 == 0
                             and self.g.convs[o["conv"]]["cin"] % 8 == 0 for o in need))   # rn_depth_to_space2x: C % 8
-        if subpixel:
-            p.R = p.S = 2
-            p.pad_top = p.pad_left = 0
-        d2s = []
-        plain_first = []   # per segment of the plain form: this launch is the first writer of its gradient buffer
+        # every other layer: dy itself (stride 1) or zero-upsampled (stride 2), written or accumulated in place
+        p = _C.attach_splitk_workspace(_C.ConvProblem(), self.splitk_ws)
+        p.opts = self.launch_opts
+        p.R = p.S = 2 if subpixel else k
+        p.stride_h = p.stride_w = 1
+        p.pad_top = p.pad_left = 0 if subpixel else k - 1 - pad
+        p.act, p.out_dtype, p.num_segments = _C.RN_ACT_NONE, _C.RN_DT_BF16, len(need)
+        ups, post, firsts = [], [], []   # rn_upsample_zero2x before the launch; per-segment arguments of the form's post-op
+        post_op = ((lib.rn_depth_to_space2x, "rn_depth_to_space2x") if subpixel else
+                   (lib.rn_scatter_add2x, "rn_scatter_add2x") if lowres else None)
+        fl = by = 0
         for i, op in enumerate(need):
             c = self.g.convs[op["conv"]]
+            cin = c["cin"]
             dy = dy_of[op["out"]]
             cw = dy.shape[3]
             cwp = lib.rn_conv_cin_pad(cw)     # K of the dgrad GEMM, zero padded in the packed weights only
             if op["conv"] not in packs:
-                if subpixel:
-                    buf = torch.empty((lib.rn_conv_cout_pad(4 * c["cin"]), 2, 2, cwp), dtype=self.h16, device=self.dev)
-                else:
-                    buf = torch.empty((lib.rn_conv_cout_pad(c["cin"]), k, k, cwp), dtype=self.h16, device=self.dev)
-                packs[op["conv"]] = buf
+                shape = (lib.rn_conv_cout_pad(4 * cin), 2, 2, cwp) if subpixel else (lib.rn_conv_cout_pad(cin), k, k, cwp)
+                packs[op["conv"]] = torch.empty(shape, dtype=self.h16, device=self.dev)
                 off, _ = self.p_off[c.get("kvar", op["conv"] + "/kernel")]
-                self.dgrad_packs.append((self.P.data_ptr() + 4 * off, k, c["cin"], c["cout"], cwp, buf, 1 if subpixel else 0))
+                self.dgrad_packs.append((self.P.data_ptr() + 4 * off, k, cin, c["cout"], cwp, packs[op["conv"]],
+                                         1 if subpixel else 0))
             x = self._src(op["inp"])
             H, W = x.shape[1], x.shape[2]
+            gbuf, first = self._grad_target(op["inp"], mark)
+            firsts.append(first)
+            # what the forms differ in: source, destination, output channels, residual, post-op arguments
+            src, dst, cout, res = dy, gbuf, cin, None
             if subpixel:
-                gbuf = self._gradbuf(op["inp"])
-                first = mark(op["inp"] if op["inp"] not in self.bal_src else "bal:" + op["inp"])
-                tmp = torch.empty((B, dy.shape[1], dy.shape[2], 4 * c["cin"]), dtype=self.h16, device=self.dev)
-                self._keep.append(tmp)
-                d2s.append((tmp.data_ptr(), gbuf.data_ptr(), B, dy.shape[1], dy.shape[2], c["cin"], 0 if first else 1))
-                s = p.seg[i]
-                s.x, s.w, s.y = dy.data_ptr(), packs[op["conv"]].data_ptr(), tmp.data_ptr()
-                s.scale, s.shift, s.residual = None, None, None
-                s.N, s.H, s.W, s.Cin, s.pix_stride = B, dy.shape[1], dy.shape[2], cw, cw
-                s.Ho, s.Wo, s.Cout = dy.shape[1], dy.shape[2], 4 * c["cin"]
-                continue
-            if lowres:
-                gbuf = self._gradbuf(op["inp"])
-                first = mark(op["inp"] if op["inp"] not in self.bal_src else "bal:" + op["inp"])
-                tmp = torch.empty((B, dy.shape[1], dy.shape[2], c["cin"]), dtype=self.h16, device=self.dev)
-                self._keep.append(tmp)
-                scatters.append((tmp.data_ptr(), gbuf.data_ptr(), B, dy.shape[1], dy.shape[2], c["cin"], H, W,
-                                 0 if first else 1))
-                s = p.seg[i]
-                s.x, s.w, s.y = dy.data_ptr(), packs[op["conv"]].data_ptr(), tmp.data_ptr()
-                s.scale, s.shift, s.residual = None, None, None
-                s.N, s.H, s.W, s.Cin, s.pix_stride = B, dy.shape[1], dy.shape[2], cw, cw
-                s.Ho, s.Wo, s.Cout = dy.shape[1], dy.shape[2], c["cin"]
-                continue
-            if stride == 2:
-                up = torch.empty((B, H, W, cw), dtype=self.h16, device=self.dev)
-                ups.append((dy.data_ptr(), up.data_ptr(), B, dy.shape[1], dy.shape[2], cw, H, W))
-                self._keep.append(up)
-                src = up
-            elif stride == 1:
-                src = dy
+                cout = 4 * cin
+                dst = torch.empty((B, dy.shape[1], dy.shape[2], cout), dtype=self.h16, device=self.dev)
+                post.append((dst.data_ptr(), gbuf.data_ptr(), B, dy.shape[1], dy.shape[2], cin, 0 if first else 1))
+            elif lowres:
+                dst = torch.empty((B, dy.shape[1], dy.shape[2], cin), dtype=self.h16, device=self.dev)
+                post.append((dst.data_ptr(), gbuf.data_ptr(), B, dy.shape[1], dy.shape[2], cin, H, W, 0 if first else 1))
             else:
-                raise NotImplementedError("stride > 2")
-            gbuf = self._gradbuf(op["inp"])
-            first = mark(op["inp"] if op["inp"] not in self.bal_src else "bal:" + op["inp"])
-            plain_first.append(first and stride == 1)
+                if stride == 2:
+                    src, up_args = self._zero_upsampled(dy, H, W)
+                    ups.append(up_args)
+                res = None if first else gbuf.data_ptr()
+            if dst is not gbuf:
+                self._keep.append(dst)
             s = p.seg[i]
-            s.x, s.w, s.y = src.data_ptr(), packs[op["conv"]].data_ptr(), gbuf.data_ptr()
-            s.scale, s.shift = None, None
-            s.residual = None if first else gbuf.data_ptr()
+            s.x, s.w, s.y = src.data_ptr(), packs[op["conv"]].data_ptr(), dst.data_ptr()
+            s.scale, s.shift, s.residual = None, None, res
             s.N, s.H, s.W, s.Cin, s.pix_stride = B, src.shape[1], src.shape[2], cw, cw
-            s.Ho, s.Wo, s.Cout = H, W, c["cin"]
-        # stage 1 of the BatchNorm backward reduction of the layers whose dz this launch writes (all segments or none)
-        bn_fused = 0
-        hits = [self._bn_bwd_fusable(op["inp"]) for op in need] if len(plain_first) == len(need) and all(plain_first) else []
-        # all segments of a BatchNorm problem or none (rn_bn_bwd_reduce): a problem is switched over once the launches
-        # planned so far write dz of EVERY one of its segments, each exactly once — one launch for a bottleneck layer,
-        # one launch over both heads x five levels for head-tower depths 0-2, the two prediction convs' data gradients
-        # together for depth 3.  Until then the assignments wait in self._bn_bwd_pending; the rn_conv_problem structs
-        # are read at launch time, so they can still be patched when the last segment turns up.
-        if hits and all(h is not None for h in hits):
-            for i, (op, (pb, j)) in enumerate(zip(need, hits)):
-                pend = self._bn_bwd_pending.setdefault(id(pb), {"pb": pb, "seg": {}})
-                if j in pend["seg"]:          # a second writer: not a single-consumer layer after all
-                    pend["dead"] = True
-                pend["seg"][j] = (p, i, op["inp"], None)
-            for key in {id(pb) for pb, _ in hits}:
-                pend = self._bn_bwd_pending[key]
-                pb = pend["pb"]
-                if pend.get("dead") or pend.get("done") or sorted(pend["seg"]) != list(range(pb.num_segments)):
-                    continue
-                pend["done"] = True
-                for j, (pc_, i_, _, _) in pend["seg"].items():
-                    pb.seg[j].ext_chunks_bwd = lib.rn_conv_bn_row_blocks(ctypes.byref(pc_), i_)
-                wsb = torch.zeros((max(lib.rn_bn_workspace_bytes(ctypes.byref(pb)), 256),), dtype=torch.uint8, device=self.dev)
-                self.bn_bwd_ws[key] = wsb
-                for j, (cp, ci, name, _) in pend["seg"].items():
-                    sg = cp.seg[ci]
-                    sg.bn_partial = wsb.data_ptr() + lib.rn_bn_bwd_partial_offset_bytes(ctypes.byref(pb), j)
-                    sg.bn_bwd_y = self.raw[name].data_ptr()
-                    sg.bn_bwd_fwd = pb.seg[j].fwd
-                    self.bn_bwd_fused.append(name)
-                    if id(cp) in self._algo:    # an earlier launch: add the bytes of y its epilogue now reads
-                        fl0, by0 = self._algo[id(cp)]
-                        self._algo[id(cp)] = (fl0, by0 + 2 * int(pb.seg[j].P) * int(pb.seg[j].C))
-                    else:
-                        bn_fused += 2 * int(pb.seg[j].P) * int(pb.seg[j].C)
+            s.Ho, s.Wo, s.Cout = dst.shape[1], dst.shape[2], cout
+            # algorithmic work — the layer's own MACs and tensors: dy [B,Ho,Wo,Cout] in, dx [B,H,W,Cin] out (+ accumulate read)
+            Ho, Wo = self.tensors[op["out"]][:2]
+            fl += 2 * B * Ho * Wo * k * k * cin * c["cout"]
+            by += 2 * B * Ho * Wo * c["cout"] + 2 * B * H * W * cin * (2 if res else 1) + 2 * k * k * cin * c["cout"]
+        # the BatchNorm-backward epilogue takes dz as it leaves the GEMM: the plain stride-1 form, first writer everywhere
+        if post_op is None and stride == 1 and all(firsts):
+            by += self._fuse_bn_bwd(p, need)
+        self._algo[id(p)] = (fl, by)
         self._keep.append(p)
         self.conv_launches.append(("dgrad:" + (need[0].get("group") or need[0]["out"]), p))
-        fl = by = 0
-        for op in need:     # the layer's own MACs and tensors: dy [B,Ho,Wo,Cout] in, dx [B,H,W,Cin] out (+ accumulate read)
-            c = self.g.convs[op["conv"]]
-            Ho, Wo = self.tensors[op["out"]][:2]
-            x = self._src(op["inp"])
-            fl += 2 * B * Ho * Wo * c["k"] * c["k"] * c["cin"] * c["cout"]
-            by += 2 * B * Ho * Wo * c["cout"] + 2 * B * x.shape[1] * x.shape[2] * c["cin"] + 2 * c["k"] * c["k"] * c["cin"] * c["cout"]
-        by += sum(2 * B * self._src(o["inp"]).shape[1] * self._src(o["inp"]).shape[2] * self.g.convs[o["conv"]]["cin"]
-                  for i, o in enumerate(need) if p.seg[i].residual)
-        by += bn_fused
-        self._algo[id(p)] = (fl, by)
 
-        def dgrad(st, p=p, ups=ups, scatters=scatters, d2s=d2s):
+        def dgrad(st, p=p, ups=ups, post=post):
             for u in ups:
                 _C.check(lib.rn_upsample_zero2x(*u, st), "rn_upsample_zero2x")
             self._launch_conv(p, st, "dgrad")
-            for sc in scatters:
-                _C.check(lib.rn_scatter_add2x(*sc, st), "rn_scatter_add2x")
-            for ds in d2s:
-                _C.check(lib.rn_depth_to_space2x(*ds, st), "rn_depth_to_space2x")
+            for a in post:
+                _C.check(post_op[0](*a, st), post_op[1])
         self.bwd_steps.append(dgrad)
 
     # ---- one training step -----------------------------------------------------------------------------
     def refresh_dgrad_weights(self, st):
         lib = self.lib
         if self.dgrad_packs:
-            if getattr(self, "_dgrad_pack_items", None) is None:   # descriptors are static: build them once
-                arr = (_C.DgradPack * len(self.dgrad_packs))()
-                for i, (mptr, k, cin, cout, cw, buf, mode) in enumerate(self.dgrad_packs):
-                    arr[i].w_ohwi, arr[i].w_packed = mptr, buf.data_ptr()
-                    arr[i].R, arr[i].S, arr[i].Cin, arr[i].Cout, arr[i].Cout_pad, arr[i].pad_ = k, k, cin, cout, cw, mode
-                self._dgrad_pack_items = arr
             _C.check(lib.rn_pack_conv_weight_dgrad_batch(self._dgrad_pack_items, len(self.dgrad_packs), st),
                      "pack dgrad")
         for (mptr, k, C, buf) in self.dw_flip_packs:
@@ -1637,9 +1650,6 @@ class TrainEngine:
         """The dy tensors of the prediction convs (bf16 [B,H,W,padded channels]) keyed like the predictions: handed to
         RetinaNetLoss(grads_bf16=...) so that the loss kernels write the upstream gradients where backward() reads
         them (pad channels stay zero from allocation)."""
-        if getattr(self, "_loss_dy", None) is None:
-            self._loss_dy = {k: {lv: self.dy_of[name] for lv, name in self.g.outputs[k].items()}
-                             for k in ("class-predictions", "box-predictions")}
         return self._loss_dy
 
     def backward(self, loss_grads):
@@ -1654,7 +1664,7 @@ class TrainEngine:
                     C = gsrc.shape[-1]
                     _C.check(lib.rn_cast_pad_f32_to_bf16(gsrc.data_ptr(), dst.data_ptr(), gsrc.numel() // C, C,
                                                          dst.shape[3], st), "cast")
-        if getattr(self, "_dgrad_prepacked", False):     # train_step repacked them beside the forward pass
+        if self._dgrad_prepacked:     # train_step repacked them beside the forward pass
             torch.cuda.current_stream(self.dev).wait_stream(self._side_stream)
             self._dgrad_prepacked = False
         else:
@@ -1698,7 +1708,7 @@ class TrainEngine:
     # factor was != 1.  Only then is the correction sum_r (factor_r - 1) * g_r all-reduced and added — the result is
     # sum_r factor_r * g_r, the reference's clip-then-sum.
     def _plan_buckets(self):
-        bucket_bytes = int(os.environ.get("RNET_C1_BUCKET_MB", "25")) << 20
+        bucket_bytes = self._bucket_bytes
         written = {}
         for i, fn in enumerate(self.bwd_steps):
             for k in getattr(fn, "writes", ()):
@@ -1736,30 +1746,27 @@ class TrainEngine:
         self._overlap_on = on
         if not on:
             return False
-        if getattr(self, "_buckets", None) is None:
+        if self._buckets is None:
             self._plan_buckets()
             # Which stream prepares a bucket and hands it to RCCL.  Round 3 used a third stream of its own; round 5 measured
             # (tools/probes/dp_overlap_trace.py, 1-rank nccl group on one MI355X, rocprofv3 kernel trace) that HIP mapped
             # it onto the SAME hardware queue as the weight-gradient stream: a bucket's "wait for the main stream" packet
             # then sat in front of weight-gradient kernels that had nothing to wait for — 2.3 ms of chip idle per step
             # against 0.7 ms, step 34.4 ms against 31.4 ms for the plain order (and 44 ms with GPU_MAX_HW_QUEUES=8) — the
-            # overlap machinery cost more than the all-reduce it hides.  Now the bucket work rides on the weight-gradient
+            # overlap machinery cost more than the all-reduce it hides.  So the bucket work rides on the weight-gradient
             # stream itself (most of a bucket's producers are there; it waits for the main stream's BatchNorm gamma / beta
             # gradients through one event per bucket) or, in the one-stream backward, on the main stream: no extra queue.
-            # RNET_C1_STREAM=own restores the third stream (A/B on a multi-GPU node).
-            self._comm_stream = None
-            if os.environ.get("RNET_C1_STREAM", "side") == "own":
-                self._comm_stream, _ = _C.concurrent_stream(
-                    self.lib, self.dev, [torch.cuda.current_stream(self.dev)] + ([self._side_stream] if self._side_stream else []))
-            self._comm_events = [(torch.cuda.Event(), torch.cuda.Event()) for _ in self._buckets]
+            self._comm_events = [torch.cuda.Event() for _ in self._buckets]
             self.L = torch.zeros_like(self.G)      # what this rank contributed (for the clip correction)
+            self._flag_host = torch.zeros((1,), dtype=torch.float32, pin_memory=True)
+            self._flag_event = torch.cuda.Event()
             if self.dp_active:
                 import torch.distributed as dist
                 self._probe_bucket_group = True
                 # its own communicator: the latency-bound SyncBN all-reduces of the main stream must not queue
                 # behind a 25 MB bucket on the same RCCL stream
                 self.pg_c1 = dist.new_group(backend=dist.get_backend(self.pg))
-        if getattr(self, "_probe_bucket_group", False):
+        if self._probe_bucket_group:
             self._probe_bucket_group = False
             if self.native_comm_buckets is None and not self._bucket_group_is_safe():
                 # c10d's stream for the bucket group shares a hardware queue with the main stream: every bucket's "wait for
@@ -1769,7 +1776,7 @@ class TrainEngine:
                 logging.warning("gradient-bucket overlap disabled: c10d's stream for the bucket group blocks the main stream "
                                 "on this process's hardware-queue map (RNET_STREAM_PROBE=0 skips the probe)")
                 self._overlap_unsafe = True
-        if getattr(self, "_overlap_unsafe", False):
+        if self._overlap_unsafe:
             self._overlap_on = False
             return False
         self._overlap_done = 0
@@ -1783,7 +1790,7 @@ class TrainEngine:
         that fails is replaced by a fresh one, three times at most."""
         import torch.distributed as dist
         side = self._side_stream
-        if side is None or os.environ.get("RNET_STREAM_PROBE", "1") == "0" or dist.get_backend(self.pg_c1) != "nccl":
+        if side is None or not self._stream_probe or dist.get_backend(self.pg_c1) != "nccl":
             return True
         main = torch.cuda.current_stream(self.dev)
         tiny = torch.zeros((64,), dtype=torch.float32, device=self.dev)
@@ -1822,19 +1829,11 @@ class TrainEngine:
             self._launch_bucket(j, main, side)
 
     def _launch_bucket(self, j, main, side):
-        lib, bkt, comm = self.lib, self._buckets[j], self._comm_stream
-        e_main, e_side = self._comm_events[j]
-        if comm is None:             # the weight-gradient stream (or the only stream) carries the bucket work
-            comm = side if side is not None else main
-            if side is not None:
-                e_main.record(main)
-                side.wait_event(e_main)
-        else:
-            e_main.record(main)
-            comm.wait_event(e_main)
-            if side is not None:
-                e_side.record(side)
-                comm.wait_event(e_side)
+        lib, bkt = self.lib, self._buckets[j]
+        comm = side if side is not None else main   # the weight-gradient stream (or the only stream) carries the bucket work
+        if side is not None:
+            self._comm_events[j].record(main)
+            side.wait_event(self._comm_events[j])
         self._bucket_stream = comm
         cst = ctypes.c_void_p(comm.cuda_stream)
         a = self._step_args
@@ -1850,7 +1849,7 @@ class TrainEngine:
                 _C.check(lib.rn_optim_clip_factors(self.segs_dev.data_ptr(), self.n_segs, self.n_blocks, a["clip"],
                                                    a["alpha"], self.metrics.data_ptr(), self.G.data_ptr(),
                                                    self.opt_ws.data_ptr(), self.opt_ws.numel(), cst), "rn_optim_clip_factors")
-            if self.dp_active and getattr(self, "native_comm_buckets", None) is not None:
+            if self.dp_active and self.native_comm_buckets is not None:
                 # rn_allreduce_bucket (rn_comm.hip): one ncclAllReduce on the bucket's stream, behind its prepare kernel
                 self.native_comm_buckets.all_reduce_bucket(self.G[bkt["begin"]:bkt["end"]])
             elif self.dp_active:
@@ -1859,11 +1858,11 @@ class TrainEngine:
                 t0 = _time.perf_counter()
                 self._overlap_works.append(dist.all_reduce(self.G[bkt["begin"]:bkt["end"]], group=self.pg_c1,
                                                            async_op=True))
-                self.bucket_host_ms = max(getattr(self, "bucket_host_ms", 0.0), (_time.perf_counter() - t0) * 1e3)
+                self.bucket_host_ms = max(self.bucket_host_ms, (_time.perf_counter() - t0) * 1e3)
         self._overlap_last_event = torch.cuda.Event()
         self._overlap_last_event.record(comm)
 
-    def _overlap_finish(self, optimistic_sgd=None):
+    def _overlap_finish(self, optimistic_sgd):
         """After the join: wait for the buckets; when some rank's clip fired, all-reduce the correction.
         optimistic_sgd: callable that enqueues the SGD kernel with the device-side predicate "G[0] == 0" (no clip fired on
         any rank, no gradient non-finite: the common case).  The flag goes to pinned host memory with an asynchronous copy
@@ -1874,23 +1873,18 @@ class TrainEngine:
         cur = torch.cuda.current_stream(self.dev)
         for w in self._overlap_works:
             w.wait()
-        if getattr(self, "_bucket_stream", None) is not None and self._bucket_stream != cur:
+        if self._bucket_stream is not None and self._bucket_stream != cur:
             cur.wait_stream(self._bucket_stream)
         applied = False
-        if getattr(self, "price_without_flag_read", False):
+        if self.price_without_flag_read:
             fired = False                            # bench.py's extra.dp_overhead ONLY: what the host read below costs
-        elif optimistic_sgd is not None:
-            if getattr(self, "_flag_host", None) is None:
-                self._flag_host = torch.zeros((1,), dtype=torch.float32, pin_memory=True)
-                self._flag_event = torch.cuda.Event()
+        else:
             self._flag_host.copy_(self.G[0:1], non_blocking=True)
             self._flag_event.record(cur)
             optimistic_sgd()                         # predicate on the device: a no-op when G[0] != 0
             self._flag_event.synchronize()
             fired = float(self._flag_host[0]) != 0.0
             applied = not fired
-        else:
-            fired = float(self.G[0].item()) != 0.0      # one host sync per step: the collective below is conditional
         self.clip_fired = fired
         if not fired:
             return applied
@@ -1920,8 +1914,7 @@ class TrainEngine:
         if overlapped:
             # G[0] = sum over the ranks of "a clip factor != 1 or the gradient norm is not finite" (rn_optim_clip_factors:
             # a non-finite norm makes its factor != 1, so G[0] == 0 also says every gradient is finite)
-            optimistic = os.environ.get("RNET_C1_OPTIMISTIC_SGD", "1") != "0"
-            applied = self._overlap_finish((lambda: sgd(self.G.data_ptr())) if optimistic else None)
+            applied = self._overlap_finish(lambda: sgd(self.G.data_ptr()))
             if applied:
                 self.refresh_packs()
                 if self.loss_scale:
@@ -1955,7 +1948,7 @@ class TrainEngine:
         after it has enqueued its forward pass (or finish_step(), for whoever reads the counters in between).  Reading
         it here (`.item()`) drained the queue at the end of every mixed_float16 step: the device then idled ~1 ms at the
         head of the next step until the host had launched its first kernels (tools/trace_gaps.py on configs[4])."""
-        if getattr(self, "_ls_host", None) is None:
+        if self._ls_host is None:
             self._ls_host = torch.zeros((1,), dtype=torch.float32, pin_memory=True)
             self._ls_event = torch.cuda.Event()
         self._ls_host.copy_(self.G[1:2], non_blocking=True)
@@ -1963,7 +1956,7 @@ class TrainEngine:
         self._ls_pending = True
 
     def _resolve_loss_scale(self):
-        if not getattr(self, "_ls_pending", False):
+        if not self._ls_pending:
             return
         self._ls_pending = False
         self._ls_event.synchronize()

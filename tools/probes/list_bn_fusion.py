@@ -10,7 +10,8 @@ b = ModelBuilder(p, "train", device=dev, seed=1337)
 m = b()
 eng = TrainEngine(m, 32, frozen_regexes=[b.FREEZE_VARS_REGEX[n] for n in p.training.freeze_variables], world_size=1)
 fused = set(eng.bn_bwd_fused)
-for pb, _, _, _, _, gops in eng.bn_groups.values():
-    for i, o in enumerate(gops):
+for grp in eng.bn_groups.values():
+    pb = grp.problem
+    for i, o in enumerate(grp.ops):
         if o.get("act") == "relu" and not o.get("residual") and eng._bn_trainable(o):
             print(o["out"], "fused" if o["out"] in fused else "NOT fused", "consumers", len(eng.readers.get(o["out"], [])), "P", int(pb.seg[i].P), "C", int(pb.seg[i].C))

@@ -11,10 +11,12 @@ from bench_train import synth_targets
 
 def describe(f):
     from retinanet import _C
-    objs = list(f.__defaults__ or ())
+    objs = list(f.__defaults__ or ()) + [c.cell_contents for c in f.__closure__ or ()]
     for o in list(objs):
         if isinstance(o, tuple):
             objs += list(o)
+        elif getattr(o, "__defaults__", None):    # the launch that a BatchNorm-training step wraps
+            objs += list(o.__defaults__)
     for o in objs:
         tgt = getattr(o, "_obj", o)           # ctypes.byref(...) keeps the structure in _obj
         if isinstance(tgt, _C.ConvProblem):
