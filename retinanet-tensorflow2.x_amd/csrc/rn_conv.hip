@@ -12,8 +12,9 @@
 // 4 wavefronts (2x2), tile BM x BN x BK = 128 x {128,64} x {64,32} — that serves the narrow layers and the
 // small launches; layers with Cout >= 256 and enough tiles go to the persistent 256 x 256 x 32 kernel in
 // rn_conv_big.hip (conv_use_big below).
-//   * staging by `buffer_load ... lds` DMA (16 B per lane, no VGPR round trip), two LDS stages, ONE
-//     barrier per K step: the DMA of step t+1 is issued before the MFMAs of step t.
+//   * staging by `buffer_load ... lds` DMA (16 B per lane, no VGPR round trip) into a ring of three or four LDS
+//     stages — as many as leave two workgroups per CU (launch_conv) — with counted waits and ONE s_barrier per
+//     K step: the DMA of step t + STAGES - 1 is issued before the MFMAs of step t.
 //   * LDS tiles are [rows][BK] bf16 with the 16-byte slot index XOR-swizzled by
 //     (row / rows_per_256B) — applied to the DMA's per-lane source chunk and to the ds_read_b128
 //     fragment address — so the fragment reads (one row per lane, same k slot) hit 16 distinct
@@ -35,10 +36,9 @@
 #include <algorithm>
 #include "rn_conv_dev.h"
 
-// ABL: ablation mask for tools/bench_conv.py (0 in production): 1 = B tile loaded once,
-// 2 = A tile loaded once, 4 = no MFMA.
-// WM x WN wavefronts (64 x (BN/WN) wave tiles), two LDS stages: 128 x {128,64} x {64,32}, 2x2 waves
-// (64 KB LDS, 2 workgroups/CU) for the narrow / small launches; the wide layers go to rn_conv_big.hip.
+// 2 x 2 wavefronts (64 x (BN/2) wave tiles): 128 x {128,64} x {64,32} for the narrow / small launches; the wide layers
+// go to rn_conv_big.hip.  STAGES (launch_conv picks it from the tile's bytes): 3 or 4 = that many whole LDS stages,
+// 32 = three stages of pixels and two of weights (128 x 128 x 64); 48 - 80 KB of LDS, two workgroups per CU.
 // SPLIT (rnet_hip.h: rn_conv_problem.splitk_ws; small launches of deep layers — batch-1 / batch-8 inference): every tile is
 // cut along K into args.split_s parts, one workgroup each (grid = total_tiles * split_s, the parts of a tile neighbours in
 // the XCD-aware numbering).  A part writes its raw fp32 accumulators — in the [BM][BN] row layout the epilogue's second
@@ -46,8 +46,10 @@
 // tile's counter with a returning agent-scope atomic; the part that arrives LAST (whichever it is: nobody waits) reads
 // all slots back with sc1 loads, adds them IN PART ORDER (the same bits on every run), zeroes the counter and runs the
 // epilogue arithmetic (bias, rounding points, BatchNorm affine, residual, activation) on the sums.
-template <int BM, int BN, int BK, bool OUT_F32, int ABL = 0, int WM = 2, int WN = 2, int STAGES = 2, bool SPLIT = false>
-__global__ void __launch_bounds__(64 * WM * WN, 2) conv_fwd_kernel(const ConvArgs args) {
+template <int BM, int BN, int BK, bool OUT_F32, int STAGES, bool SPLIT>
+__global__ void __launch_bounds__(CONV_THREADS, 2) conv_fwd_kernel(const ConvArgs args) {
+  static_assert((STAGES >= 3 && STAGES <= 8) || STAGES == 32, "no K loop for this stage count");
+  constexpr int WM = 2, WN = 2;                     // wavefronts along M / N
   constexpr int NWAVES = WM * WN;
   constexpr int NTHREADS = 64 * NWAVES;
   constexpr int SLOTS = BK / 8;
@@ -178,17 +180,13 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_fwd_kernel(const ConvArg
     const int cw__ = (c0_) < cwrap ? (c0_) : ((c0_) < 2 * cwrap ? (c0_) - cwrap : (c0_) - 2 * cwrap);   \
     const unsigned tap_off__ = (unsigned)((((long long)r__ * W + s__) * PS + cw__) * 2);      \
     char* st__ = smem + (buf) * STAGE_BYTES;                                                  \
-    if (!(ABL & 2) || ((tap_) == 0 && (c0_) == 0)) {                                          \
-      _Pragma("unroll") for (int j = 0; j < A_INSTR; ++j) {                                   \
-        const unsigned v__ = ((a_mask[j] >> (tap_)) & 1u) ? a_off[j] + tap_off__ : RN_OOB;    \
-        dma16(rs_x, st__ + (j * NWAVES + wave) * 1024, v__);                                       \
-      }                                                                                       \
+    _Pragma("unroll") for (int j = 0; j < A_INSTR; ++j) {                                     \
+      const unsigned v__ = ((a_mask[j] >> (tap_)) & 1u) ? a_off[j] + tap_off__ : RN_OOB;      \
+      dma16(rs_x, st__ + (j * NWAVES + wave) * 1024, v__);                                    \
     }                                                                                         \
     const unsigned koff__ = (unsigned)(((long long)(tap_) * Cin + (c0_)) * 2);                \
-    if (!(ABL & 1) || ((tap_) == 0 && (c0_) == 0)) {                                          \
-      _Pragma("unroll") for (int j = 0; j < B_INSTR; ++j)                                     \
-        dma16(rs_w, st__ + A_BYTES + (j * NWAVES + wave) * 1024, b_off[j] + koff__);               \
-    }                                                                                         \
+    _Pragma("unroll") for (int j = 0; j < B_INSTR; ++j)                                       \
+      dma16(rs_w, st__ + A_BYTES + (j * NWAVES + wave) * 1024, b_off[j] + koff__);            \
   } while (0)
 
   int tap = 0, c0 = 0;   // coordinates of the NEXT tile to issue
@@ -206,48 +204,11 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_fwd_kernel(const ConvArg
     }                 \
   } while (0)
 
-  if (ABL & 32) {
-    // ablation: no main loop at all (launch + prologue + epilogue cost)
-  } else if (STAGES == 2) {
-    RN_ISSUE_TILE(0, tap, c0);
-    RN_ADVANCE();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int cur = 0;
-#pragma unroll 1
-    for (int kt = kbeg; kt < ksteps; ++kt) {
-      if (kt + 1 < ksteps) {
-        RN_ISSUE_TILE(cur ^ 1, tap, c0);
-        RN_ADVANCE();
-      }
-      const char* base = smem + cur * STAGE_BYTES;
-#pragma unroll
-      for (int kk = 0; kk < KSUB; ++kk) {
-        bf16x8_t fa[TM], fb[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) fa[i] = *(const bf16x8_t*)(base + rd_a[i][kk]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) fb[j] = *(const bf16x8_t*)(base + rd_b[j][kk]);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            if (!(ABL & 4)) {
-              acc[i][j] = RN_MFMA_32x32x16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-            } else {
-              acc[i][j][0] += (float)fa[i][0] + (float)fb[j][0];
-            }
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      cur ^= 1;
-    }
-  }
-  else if (STAGES >= 3 && STAGES <= 8) {
+  if (STAGES <= 8) {
     // STAGES LDS stages, counted waits: the DMA of step kt + STAGES - 1 is issued while step kt is multiplied, so a tile's
-    // bytes have STAGES - 1 steps to arrive instead of one (the two-stage loop waits for ALL outstanding pieces — i.e. for
-    // the round trip of the tile it issued at the top of the same step — before every barrier: ~1.2 us per K step whatever
-    // the step computes).  One s_barrier per step (no fence: __syncthreads() would put s_waitcnt vmcnt(0) in front of it):
+    // bytes have STAGES - 1 steps to arrive instead of one (a two-stage loop that waits for ALL outstanding pieces — i.e. for
+    // the round trip of the tile it issued at the top of the same step — before every barrier cost ~1.2 us per K step
+    // whatever the step computed).  One s_barrier per step (no fence: __syncthreads() would put s_waitcnt vmcnt(0) in front of it):
     // behind it every wave's pieces of step kt have landed and every wave has finished reading step kt - 1, whose stage
     // the next issue overwrites.
     constexpr int PIECES = A_INSTR + B_INSTR;   // DMA instructions per wave and K step
@@ -287,8 +248,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_fwd_kernel(const ConvArg
       cur = cur == STAGES - 1 ? 0 : cur + 1;
     }
     __syncthreads();   // the epilogue reuses the stages
-  }
-  else if (STAGES == 32) {
+  } else {
     // 128 x 128 x 64 (32 KB per K step; three whole stages would leave one workgroup per CU): THREE stages of pixels, TWO of
     // weights, 80 KB — two workgroups per CU.  The pixels come from HBM (or another XCD's L2) and get two steps to arrive; the
     // weights are L2-resident and get one.  Issue order per step: weights of step kt + 1, THEN pixels of step kt + 2, so that
@@ -355,17 +315,6 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_fwd_kernel(const ConvArg
 #undef RN_ISSUE_TILE
 
   // ---- epilogue ------------------------------------------------------------------------------
-  if (ABL & 16) {   // ablation: no epilogue (one never-taken store keeps the accumulators alive)
-    float t = 0.0f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += acc[i][j][r];
-    if (t == 123.456f) ((float*)sg.y)[tid] = t;
-    return;
-  }
   // fused BatchNorm backward reduction (rn_conv_segment.bn_bwd_y): the y values stage 2 needs — this thread's 4
   // channels of its BM / ROWS rows — are fetched NOW, so that their HBM latency runs under stage 1 and the barrier
   // (loaded where they are used, behind the stores of the previous row, each launch paid ~35 us for them)
@@ -528,7 +477,6 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_fwd_kernel(const ConvArg
         rn_apply_act_n<4>(f4, args.act);
         v = make_float4(f4[0], f4[1], f4[2], f4[3]);
       }
-      if ((ABL & 8) && v.x != 123.456f) continue;   // ablation: no global stores
       if (OUT_F32) {
         *(float4*)((float*)sg.y + o) = v;
       } else {
@@ -580,31 +528,22 @@ extern "C" int rn_conv_cout_pad(int Cout) { return Cout <= 64 ? 64 : (int)rn_ali
 // packed-weight channel count: Cin rounded up to the K step (32 below 64 channels, 64 above)
 extern "C" int rn_conv_cin_pad(int Cin) { return Cin <= 32 ? 32 : (int)rn_align_up((size_t)Cin, 64); }
 
-template <int BM, int BN, int BK, bool F32, bool SPLIT = false>
+template <int BM, int BN, int BK, bool F32, bool SPLIT>
 static int launch_conv(const ConvArgs& a, hipStream_t st) {
   constexpr int stage = (BM + BN) * BK * 2;
   constexpr int epi = BM * BN * 4;
   // as many stages (up to four) as leave two workgroups per CU: 128 x 64 x 64: three (72 KB); 128 x 128 x 32: four (64 KB);
-  // 128 x 64 x 32: four (48 KB); 128 x 128 x 64 keeps two (three would be 96 KB, one workgroup per CU: measured 35 - 45 %
-  // slower wherever a launch has more tiles than compute units, equal below)
-  // (32 = three stages of pixels + two of weights, 80 KB, for the 32 KB steps of 128 x 128 x 64)
-  constexpr int STAGES = (4 * stage <= 72 * 1024) ? 4 : ((3 * stage <= 72 * 1024) ? 3 : ((BM == 128 && BN == 128 && BK == 64) ? 32 : 2));
-  static const bool two_stages = getenv("RNET_CONV128_STAGES") && atoi(getenv("RNET_CONV128_STAGES")) == 2;   // A/B probe
-  if (STAGES >= 3 && two_stages) {
-    constexpr int lds2 = (2 * stage > epi) ? 2 * stage : epi;
-    auto kern2 = conv_fwd_kernel<BM, BN, BK, F32, 0, 2, 2, 2, SPLIT>;
-    if (lds2 > 48 * 1024)
-      RN_CHECK_HIP(hipFuncSetAttribute((const void*)kern2, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-    hipLaunchKernelGGL(kern2, dim3(SPLIT ? a.vtotal : a.total_tiles), dim3(256), lds2, st, a);
-    RN_CHECK_LAUNCH();
-    return RN_OK;
-  }
+  // 128 x 64 x 32: four (48 KB); 128 x 128 x 64 (32 KB per K step: three whole stages would be 96 KB, one workgroup per CU:
+  // measured 35 - 45 % slower wherever a launch has more tiles than compute units, equal below) gets 32 = three stages of
+  // pixels + two of weights, 80 KB
+  constexpr int STAGES = (4 * stage <= 72 * 1024) ? 4 : ((3 * stage <= 72 * 1024) ? 3 : 32);
+  static_assert(STAGES != 32 || (BM == 128 && BN == 128 && BK == 64), "the 3 + 2 stage ring is laid out for 128 x 128 x 64");
   constexpr int ring = STAGES == 32 ? 3 * BM * BK * 2 + 2 * BN * BK * 2 : STAGES * stage;
   constexpr int lds = (ring > epi) ? ring : epi;
-  auto kern = conv_fwd_kernel<BM, BN, BK, F32, 0, 2, 2, STAGES, SPLIT>;
+  auto kern = conv_fwd_kernel<BM, BN, BK, F32, STAGES, SPLIT>;
   if (lds > 48 * 1024)
     RN_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipLaunchKernelGGL(kern, dim3(SPLIT ? a.vtotal : a.total_tiles), dim3(256), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3(SPLIT ? a.vtotal : a.total_tiles), dim3(CONV_THREADS), lds, st, a);
   RN_CHECK_LAUNCH();
   return RN_OK;
 }
@@ -615,16 +554,6 @@ static int launch_conv128(const ConvArgs& a, int BN, int BK, bool f32, hipStream
   if (BN == 64 && BK == 64) return f32 ? launch_conv<128, 64, 64, true, SPLIT>(a, st) : launch_conv<128, 64, 64, false, SPLIT>(a, st);
   if (BN == 128 && BK == 32) return f32 ? launch_conv<128, 128, 32, true, SPLIT>(a, st) : launch_conv<128, 128, 32, false, SPLIT>(a, st);
   return f32 ? launch_conv<128, 64, 32, true, SPLIT>(a, st) : launch_conv<128, 64, 32, false, SPLIT>(a, st);
-}
-
-template <int ABL>
-static int launch_ablate(const ConvArgs& a, hipStream_t st) {
-  constexpr int lds = 2 * (128 + 128) * 64 * 2;
-  auto kern = conv_fwd_kernel<128, 128, 64, false, ABL>;
-  RN_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipLaunchKernelGGL(kern, dim3(a.total_tiles), dim3(CONV_THREADS), lds, st, a);
-  RN_CHECK_LAUNCH();
-  return RN_OK;
 }
 
 // 256 x 256 x 32 tiles (rn_conv_big.hip) for the MFMA-bound layers: every segment at least 256 output
@@ -758,14 +687,11 @@ static int conv_pick(const rn_conv_problem* p) {
 
 // K step of the 128-row kernel: 64, or 32 when the padded channel count is not a multiple of 64 — and for the shallow
 // layers (K = R S Cin <= 256: ResNet stage 1's 256 -> 64, the first 1x1 of stage 2), which are HBM-bound: four stages of half
-// the size stream better than two or three (tools/probes/ab_conv128_bk.sh: 256 -> 64 at 160 x 160, batch 32, 133.9 -> 119.3 us;
+// the size stream better than two or three (profiles/r05_ab/summary.tsv: 256 -> 64 at 160 x 160, batch 32, 133.9 -> 119.3 us;
 // 256 -> 128 194.0 -> 183.0) while every deeper layer loses 10 - 15 % to the second barrier per 16 MFMAs.
-// RNET_CONV128_BK=32 / 64 (A/B probe) forces one of them where the channel count allows.
 static int conv128_bk(const rn_conv_problem* p) {
-  static const int forced = getenv("RNET_CONV128_BK") ? atoi(getenv("RNET_CONV128_BK")) : 0;
   const int cin = rn_conv_cin_pad(p->seg[0].Cin);
-  if (cin % 64 != 0 || forced == 32) return 32;
-  if (forced == 64) return 64;
+  if (cin % 64 != 0) return 32;
   return (long long)p->R * p->S * cin <= 256 ? 32 : 64;
 }
 // Tile shape the 128-row kernel runs a problem with: BN = 64 for Cout <= 64 and for small launches (see
@@ -777,7 +703,7 @@ static int conv128_shape(const rn_conv_problem* p, int* BN_out, int* BK_out) {
     long long t128 = 0;
     for (int i = 0; i < p->num_segments; ++i)
       t128 += rn_cdiv((long long)p->seg[i].N * p->seg[i].Ho * p->seg[i].Wo, 128) * rn_cdiv(rn_conv_cout_pad(seg_cols(p->seg[i])), 128);
-    if (2 * t128 <= rn_num_cus() && !p->opts.ablate && p->opts.conv_tile != 1) BN = 64;   // conv_tile = 1 keeps 128 x 128 (tests)
+    if (2 * t128 <= rn_num_cus() && p->opts.conv_tile != 1) BN = 64;   // conv_tile = 1 keeps 128 x 128 (tests)
   }
   long long tiles = 0;
   for (int i = 0; i < p->num_segments; ++i)
@@ -791,7 +717,7 @@ static int conv128_shape(const rn_conv_problem* p, int* BN_out, int* BK_out) {
 // keeps one 16-byte load per part in flight), the slots must fit the workspace and the tiles its 4096 counters.
 #define RN_SPLIT128_MIN_STEPS 4
 static int conv128_split_parts(const rn_conv_problem* p, int tiles, int BN, int BK) {
-  if (!p->splitk_ws || p->opts.ablate || p->opts.conv_tile == 1 || tiles < 1 || tiles > 4096) return 1;
+  if (!p->splitk_ws || p->opts.conv_tile == 1 || tiles < 1 || tiles > 4096) return 1;
   int ksteps = 0x7fffffff;   // of the launch's shallowest segment
   for (int i = 0; i < p->num_segments; ++i) {
     const int terms = p->seg[i].w_terms > 1 ? p->seg[i].w_terms : 1;
@@ -1031,22 +957,6 @@ extern "C" int rn_conv2d_nhwc_fwd(const rn_conv_problem* p, void* stream) {
                "rn_conv2d_nhwc_fwd: splitk_ws must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const bool f32 = p->out_dtype == RN_DT_F32;
-  if (p->opts.ablate && BM == 128 && BN == 128 && BK == 64 && !f32) {
-    switch (p->opts.ablate) {
-      case 1: return launch_ablate<1>(a, st);
-      case 2: return launch_ablate<2>(a, st);
-      case 3: return launch_ablate<3>(a, st);
-      case 4: return launch_ablate<4>(a, st);
-      case 5: return launch_ablate<5>(a, st);
-      case 6: return launch_ablate<6>(a, st);
-      case 7: return launch_ablate<7>(a, st);
-      case 8: return launch_ablate<8>(a, st);
-      case 16: return launch_ablate<16>(a, st);
-      case 32: return launch_ablate<32>(a, st);
-      case 48: return launch_ablate<48>(a, st);
-      default: break;
-    }
-  }
   if (halo512) return rn_launch_conv_halo(a, f32, p->opts, st, 4);
   if (kid == 2) {
     rn_splitk_plan(a, conv_splitk_min_chunks(p), p->splitk_ws, p->splitk_ws_bytes, p->opts);

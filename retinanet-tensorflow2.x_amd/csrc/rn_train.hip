@@ -346,7 +346,7 @@ __global__ void __launch_bounds__(1024) bn_colreduce_final_kernel(const BnArgs a
 // partials on the 80 x 80 head level of the bench batch, 6 400 on a 160 x 160 layer (3 - 13 MB), read ONCE, cold (another
 // XCD wrote them) — and a workgroup pulls ~50 GB/s of cold lines, so the C / 16 workgroups of the form above took 11 - 41 us
 // on such launches whatever their thread layout (64 or 256 lanes per channel, 4-byte or 16-byte loads: measured,
-// tools/probes/bn_final_probe.py) where the reduction of a short segment takes 4.  Here a segment with more than
+// profiles/r05_ab/summary.tsv) where the reduction of a short segment takes 4.  Here a segment with more than
 // BN_KS_CHUNKS partial rows is cut into ks parts of ~256 rows (blockIdx.z): 1024 threads = 4 float4 columns (16 channels)
 // x 256 chunk lanes, a wave reads 16 rows x 64 contiguous bytes per load instruction; the 16 lanes of a wave that share a
 // column are added by a butterfly (xor 4 .. 32), the 16 wave sums in wave order.  Every part stores its 2 x 16 doubles
@@ -778,8 +778,7 @@ static int bn_colreduce(const rn_bn_problem* p, int mode, void* ws, size_t ws_by
   }
   int max_ks = 1;
   for (int i = 0; i < a.nseg; ++i) max_ks = a.ks[i] > max_ks ? a.ks[i] : max_ks;
-  static const int final_form = getenv("RNET_BN_FINAL") ? atoi(getenv("RNET_BN_FINAL")) : 0;   // A/B probe: 1 = never split
-  if (max_ks > 1 && final_form != 1 && (((uintptr_t)a.ws) & 15) == 0)
+  if (max_ks > 1 && (((uintptr_t)a.ws) & 15) == 0)
     hipLaunchKernelGGL(bn_colreduce_final_split_kernel, dim3((max_c + 15) / 16, a.nseg, max_ks), dim3(1024), 0, st, a);
   else
     hipLaunchKernelGGL(bn_colreduce_final_kernel<16>, dim3((max_c + 15) / 16, a.nseg), dim3(1024), 0, st, a);

@@ -313,6 +313,10 @@ def test_two_engines_in_one_process_do_not_share_launch_options(cuda):
     with pytest.raises(_C.RnetError):
         a.set_launch_opts(_C.LaunchOpts(conv_tile=4))
     assert a.launch_opts().conv_tile == 2           # a refused update leaves the handle as it was
+    with pytest.raises(_C.RnetError):
+        a.set_launch_opts(_C.LaunchOpts(ablate=1))  # the timing variants exist in the probe build only
+    oa = a.launch_opts()
+    assert (oa.conv_tile, oa.reserved_cus, oa.ablate) == (2, 8, 0)
     p = _C.ConvProblem()
     p.R = p.S = 3
     p.stride_h = p.stride_w = p.pad_top = p.pad_left = 1

@@ -59,7 +59,6 @@ def main():
     ap.add_argument("--preset", default="tower")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--ablate", type=int, default=0)
     ap.add_argument("--zeros", action="store_true", help="all-zero activations and weights (DVFS check: no toggling)")
     ap.add_argument("--halo-grid", type=int, default=0, help="limit conv_halo_kernel to this many workgroups")
     ap.add_argument("--raw", action="store_true", help="no scale / shift / activation (the training forward's raw conv output)")
@@ -70,7 +69,7 @@ def main():
     ap.add_argument("--min-tiles", type=int, default=0, help="rn_launch_opts.conv_big_min_tiles (a large value keeps a small launch on the 128-row kernel, split-K allowed)")
     a = ap.parse_args()
     lib = _C.lib()
-    opts = _C.LaunchOpts(ablate=a.ablate or 0, conv_tile=a.tile or 0, conv_no_halo=1 if a.no_halo else 0,
+    opts = _C.LaunchOpts(conv_tile=a.tile or 0, conv_no_halo=1 if a.no_halo else 0,
                          max_workgroups=a.halo_grid or 0, conv_big_min_tiles=a.min_tiles or 0)   # rn_launch_opts of every launch below
     dev = torch.device("cuda:0")
     for name in a.preset.split(","):

@@ -4,7 +4,7 @@
 # Only rn_conv_halo.hip is recompiled; the other objects come from the normal build (run `make` first).
 set -e
 cd "$(dirname "$0")/../../retinanet-tensorflow2.x_amd/csrc"
-FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt"
+FLAGS=$(make -s print-cxxflags)
 for n in "$@"; do
   /opt/rocm/bin/hipcc $FLAGS -DHALO_ABLATE=$n -DHALO_PROF -c rn_conv_halo.hip -o /tmp/rn_conv_halo_ab$n.o
   objs=$(ls build/*.o | grep -v rn_conv_halo.o)
