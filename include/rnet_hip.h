@@ -297,7 +297,7 @@ typedef struct {
    * last round in a second launch, each cut along K (input-channel chunks, >= 4 per part, <= 4 parts) over several
    * workgroups: every part writes its fp32 accumulators here and counts itself in; the part that arrives LAST adds them
    * IN PART ORDER (deterministic: the same bits on every run, whoever arrives last) and runs the normal epilogue.  Nobody
-   * waits for a partner: no spin, no timeout.  The 128-row kernel splits the same way (rn_conv.hip: small launches of
+   * waits for a partner: no spin, no timeout.  The 128-row kernel splits the same way (rn_conv_dispatch.hip: small launches of
    * deep layers, every tile cut along K).  NULL / too small: whole tiles only.
    * rn_conv_splitk_workspace_bytes() = what this problem can use on the current device (0: it would not split).
    * Launches that share a workspace must be ordered on one stream.
@@ -312,6 +312,10 @@ typedef struct {
 } rn_conv_problem;
 
 int rn_conv2d_nhwc_fwd(const rn_conv_problem* problem /* host */, void* stream);
+/* The four queries below (rn_conv_splitk_workspace_bytes, rn_conv_tile_rows, rn_conv_bn_row_blocks, rn_conv_kernel_id) and
+ * the launch read ONE plan of the problem (rn_conv_dispatch.hip: conv_plan), a pure function of the descriptor and the
+ * device's compute-unit count: what a query answers is what the launch does.  rn_conv_splitk_workspace_bytes plans as if a
+ * workspace of rn_conv_splitk_workspace_max_bytes() were attached when splitk_ws is NULL. */
 size_t rn_conv_splitk_workspace_bytes(const rn_conv_problem* problem /* host */);
 /* enough for any problem on any device (64 MB + 16 KB).  The dispatcher also looks at splitk_ws: a 3x3 / stride 1 launch
  * of fewer 256-row tiles than compute units (ResNet stage 3 / 4 at batch 8) goes to the halo kernel, every tile split,
@@ -321,17 +325,17 @@ size_t rn_conv_splitk_workspace_max_bytes(void);
 /* HWIO f32 [R,S,Cin,Cout] (the Keras kernel layout, resnet.py:137-144) -> bf16
  * [Cout_pad,R,S,Cin_pad], zero padded.  Cout_pad = rn_conv_cout_pad(Cout). */
 int rn_conv_cout_pad(int Cout);
-/* M-tile height the dispatcher picks for this problem: 256 = conv_big_kernel / conv_halo_kernel (256x256x32), 512 =
+/* M-tile height of the problem's plan: 256 = conv_big_kernel / conv_halo_kernel (256x256x32), 512 =
  * conv_halo_kernel's 512x128 form (3x3, 64 < Cout <= 128), 128 = conv_fwd_kernel<128,...>; 0 on a malformed problem.  A
  * launch with fused BatchNorm partial sums writes (rows / 128) * ceil(N*Ho*Wo / rows) 128-pixel row blocks per segment. */
 int rn_conv_tile_rows(const rn_conv_problem* problem);
 /* 128-pixel row blocks of fused BatchNorm partial sums (rn_conv_segment.bn_partial / bn_bwd_y) the launch writes for
- * `segment` — what rn_bn_segment.ext_chunks / ext_chunks_bwd must be set to.  (rows / 128) * ceil(N*Ho*Wo / rows) with
+ * `segment` (the plan's per-segment count) — what rn_bn_segment.ext_chunks / ext_chunks_bwd must be set to.  (rows / 128) * ceil(N*Ho*Wo / rows) with
  * rows = rn_conv_tile_rows(), except for conv_big_kernel launches that run BALANCED tiles (HBM-bound single-segment 1x1
  * layers whose 256-row tiles would leave the last round of the persistent grid mostly idle are cut into tiles of fewer
  * rows, same number of rounds: two blocks per tile, the second one short).  0 on a malformed problem. */
 int rn_conv_bn_row_blocks(const rn_conv_problem* problem, int segment);
-/* Which kernel rn_conv2d_nhwc_fwd runs for `problem`: 0 = 128-row tiles (conv_fwd_kernel), 1 = conv_big_kernel
+/* Which kernel rn_conv2d_nhwc_fwd runs for `problem` (the plan's kernel id): 0 = 128-row tiles (conv_fwd_kernel), 1 = conv_big_kernel
  * (256 x 256 x 32, persistent), 2 = conv_halo_kernel (256 x 256 x 32 for 3x3 / stride 1 / pad 1: pixels staged
  * once per channel chunk as a halo patch), 3 = conv_halo_kernel with 512 x 128 tiles (the same for 64 < Cout <= 128).
  * Profiling / bench bookkeeping only. */

@@ -8,10 +8,10 @@
 // prepacked weight [Cout_pad][R*S*Cin] (k contiguous), accumulation fp32 on
 // v_mfma_f32_32x32x16_bf16.
 //
-// This file: host entry points, weight / image packing, and the 128-row kernel — workgroup = 256 threads =
+// This file: weight / image packing, and the 128-row kernel — workgroup = 256 threads =
 // 4 wavefronts (2x2), tile BM x BN x BK = 128 x {128,64} x {64,32} — that serves the narrow layers and the
 // small launches; layers with Cout >= 256 and enough tiles go to the persistent 256 x 256 x 32 kernel in
-// rn_conv_big.hip (conv_use_big below).
+// rn_conv_big.hip.  Which launch gets which kernel: rn_conv_dispatch.hip (conv_plan).
 //   * staging by `buffer_load ... lds` DMA (16 B per lane, no VGPR round trip) into a ring of three or four LDS
 //     stages — as many as leave two workgroups per CU (launch_conv) — with counted waits and ONE s_barrier per
 //     K step: the DMA of step t + STAGES - 1 is issued before the MFMAs of step t.
@@ -29,11 +29,6 @@
 //   * blockIdx -> tile map is XCD aware: consecutive tiles (same A rows, neighbouring n tiles)
 //     land on the same XCD's L2 (blocks are dispatched round-robin over the 8 XCDs).
 // Roofline: MFMA-bound for K >= ~512; the small-K 1x1 convs of ResNet stage 1-2 are HBM-bound.
-#include <map>
-#include <mutex>
-#include <tuple>
-
-#include <algorithm>
 #include "rn_conv_dev.h"
 
 // 2 x 2 wavefronts (64 x (BN/2) wave tiles): 128 x {128,64} x {64,32} for the narrow / small launches; the wide layers
@@ -523,11 +518,7 @@ __global__ void __launch_bounds__(CONV_THREADS, 2) conv_fwd_kernel(const ConvArg
   }
 }
 
-// ---- host side ---------------------------------------------------------------------------------
-extern "C" int rn_conv_cout_pad(int Cout) { return Cout <= 64 ? 64 : (int)rn_align_up((size_t)Cout, 128); }
-// packed-weight channel count: Cin rounded up to the K step (32 below 64 channels, 64 above)
-extern "C" int rn_conv_cin_pad(int Cin) { return Cin <= 32 ? 32 : (int)rn_align_up((size_t)Cin, 64); }
-
+// ---- host side: the launch (rn_conv_dev.h: rn_launch_conv128) ----------------------------------
 template <int BM, int BN, int BK, bool F32, bool SPLIT>
 static int launch_conv(const ConvArgs& a, hipStream_t st) {
   constexpr int stage = (BM + BN) * BK * 2;
@@ -555,431 +546,8 @@ static int launch_conv128(const ConvArgs& a, int BN, int BK, bool f32, hipStream
   if (BN == 128 && BK == 32) return f32 ? launch_conv<128, 128, 32, true, SPLIT>(a, st) : launch_conv<128, 128, 32, false, SPLIT>(a, st);
   return f32 ? launch_conv<128, 64, 32, true, SPLIT>(a, st) : launch_conv<128, 64, 32, false, SPLIT>(a, st);
 }
-
-// 256 x 256 x 32 tiles (rn_conv_big.hip) for the MFMA-bound layers: every segment at least 256 output
-// channels wide, and enough tiles to fill the 256 CUs (one workgroup per CU) a few times over.
-// (rn_launch_opts: conv_tile forces either family, conv_big_min_tiles moves the threshold.)
-// Last-round split of a persistent launch (rnet_hip.h: rn_conv_problem.splitk_ws).  G0 workgroups walk `total` tiles in
-// rounds; the L = total mod G0 tiles of the last round are each cut into S = min(G0 / L, chunks / 4, 4) parts along K, so
-// that round keeps L * S workgroups busy for 1/S of a tile (+ the exchange of L * (S - 1) accumulator tiles through the
-// workspace) instead of L workgroups for a whole one.
-// GEMM columns of a segment: its output channels, or for w_pair (two weight planes along Cout) the packed rows
-extern "C" int rn_conv_pair_rows(int Cout) { return Cout > 0 ? 128 * ((Cout + 63) / 64) : 0; }
-static int seg_cols(const rn_conv_segment& s) { return s.w_pair ? rn_conv_pair_rows(s.Cout) : s.Cout; }
-// channel granularity of the 256- / 512-row epilogues: 16-byte rows of bf16, or of f32 (float4 stores)
-static bool seg_cout_ok(const rn_conv_problem* p, const rn_conv_segment& s) {
-  return s.Cout % (p->out_dtype == RN_DT_F32 && s.w_pair ? 4 : 8) == 0;
-}
-
-static int splitk_parts(int total, int min_chunks, int G0, long long* bytes) {
-  const int L = total % G0;
-  if (bytes) *bytes = 0;
-  if (L == 0 || L > 511 || min_chunks < 8) return 1;   // 8 arrival counters per leftover tile in a 4096-word header
-  // every part costs its tile one more 256 KB slot to write and part 0 one more to read (~4 us each): at least 4 chunks
-  // (36 K steps, ~20 us) per part, at most 4 parts
-  int S = G0 / L;
-  if (S > min_chunks / 4) S = min_chunks / 4;
-  if (S > 4) S = 4;
-  if (S < 2) return 1;
-  if (bytes) *bytes = RN_SPLITK_HEADER_BYTES + (long long)L * S * RN_SPLITK_SLOT_BYTES;   // one slot per part
-  return S;
-}
-
-static bool conv_halo_shape(const rn_conv_problem* p, int BM);
-static int conv_min_chunks(const rn_conv_problem* p);
-
-static bool conv_use_big(const rn_conv_problem* p) {
-  if (p->opts.conv_tile == 1 || p->opts.conv_tile == 3) return false;
-  long long tiles256 = 0;
-  for (int i = 0; i < p->num_segments; ++i) {
-    const rn_conv_segment& s = p->seg[i];
-    if (rn_conv_cout_pad(seg_cols(s)) < 256 || !seg_cout_ok(p, s)) return false;
-    if (s.bias && s.residual) return false;   // the residual variants of the 256-row kernels carry no bias path
-    tiles256 += rn_cdiv((long long)s.N * s.Ho * s.Wo, 256) * rn_cdiv(seg_cols(s), 256);
-  }
-  if (p->opts.conv_tile == 2 || tiles256 >= (p->opts.conv_big_min_tiles > 0 ? p->opts.conv_big_min_tiles : 192)) return true;
-  // A launch of fewer tiles than compute units (batch-8 inference, ResNet stage 3 / 4) stays on the 128-row kernel.  Round 4
-  // sent it to the halo kernel's 256 x 256 tiles, every tile cut along K, when a split-K workspace was attached; with the
-  // counted-wait K loop of the 128-row kernel (and its own split-K) that choice loses: stage-3 3x3 at batch 8 43.7 vs 36.0 us,
-  // batch 16 53.2 vs 46.1; stage-4 3x3 45.3 vs 42.6 at batch 8, 59.4 vs 61.4 at batch 16 (tools/probes/ab_small_3x3.sh); the
-  // five-level head / FPN launches at batch 1: 46.6 vs 43.9, 63.9 vs 47.0, 41.8 vs 32.9 (tools/probes/ab_b1_heads.sh).
-  // rn_launch_opts.conv_tile = 2 still takes a small launch to the halo kernel, split when a workspace is attached.
-  return false;
-}
-
-// 3x3 / stride 1 / pad 1 launches of the 256-row class go to the halo kernel (rn_conv_halo.hip) when every
-// segment's worst tile fits its patch buffer.
-static bool conv_halo_shape(const rn_conv_problem* p, int BM) {   // BM: pixels per tile (256, or 512 for the narrow form)
-  if (p->opts.conv_no_halo) return false;
-  if (p->R != 3 || p->S != 3 || p->stride_h != 1 || p->stride_w != 1 || p->pad_top != 1 || p->pad_left != 1)
-    return false;
-  static std::mutex mu;
-  static std::map<std::tuple<int, int, int, int>, int> patch_px;   // (N, H, W, pitch * 1024 + BM) -> worst patch, computed once
-  for (int i = 0; i < p->num_segments; ++i) {
-    const rn_conv_segment& s = p->seg[i];
-    if (s.Ho != s.H || s.Wo != s.W || s.Cin % 32 != 0) return false;
-    if ((long long)s.N * s.H * s.W >= (1ll << 22)) return false;   // the kernel's float-reciprocal divisions
-    int px;
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      // the wide pitch when its patch fits, else the tight one (the kernel is told per segment: halo_pitch)
-      for (int pitch : {rn_conv_halo_pitch(s.W), s.W + 1}) {
-        auto key = std::make_tuple(s.N, s.H, s.W, pitch * 1024 + BM);
-        auto it = patch_px.find(key);
-        if (it == patch_px.end()) it = patch_px.emplace(key, rn_conv_halo_patch_pixels(s.N, s.H, s.W, pitch, BM)).first;
-        px = it->second;
-        if (px <= rn_conv_halo_capacity(BM)) break;
-      }
-    }
-    if (px > rn_conv_halo_capacity(BM)) return false;
-  }
-  return true;
-}
-
-// 3x3 / stride 1 / pad 1 layers with 64 < Cout <= 128 (ResNet stage 2: 128 -> 128 at 80 x 80, forward and data gradient):
-// the halo kernel with 512 x 128 tiles (rn_conv_halo.hip, HaloGeo<4>: 4 x 2 waves of 128 pixels x 64 channels).  On the
-// 128-row kernel such a layer staged its pixels once per tap (the LDS-DMA path bound it at ~550 TFLOP/s); in a 256-wide
-// tile of the halo kernel half the waves multiply zero rows.
-static bool conv_use_halo512(const rn_conv_problem* p) {
-  if (p->opts.conv_tile == 1 || p->opts.conv_no_halo) return false;
-  long long tiles = 0;
-  for (int i = 0; i < p->num_segments; ++i) {
-    const rn_conv_segment& s = p->seg[i];
-    const int cp = rn_conv_cout_pad(seg_cols(s));
-    // conv_tile = 3: any width, also <= 64 channels (half of the tile's columns are then zero weights)
-    if ((cp % 128 != 0 && !(cp == 64 && p->opts.conv_tile == 3)) || (cp != 128 && p->opts.conv_tile != 3) || !seg_cout_ok(p, s))
-      return false;
-    if (s.bias && s.residual) return false;   // as for the 256-row kernels: the residual variants carry no bias path
-    tiles += rn_cdiv((long long)s.N * s.Ho * s.Wo, 512) * rn_cdiv(cp, 128);
-  }
-  if (!conv_halo_shape(p, 512)) return false;
-  // enough tiles to fill the chip once (opts.conv_tile = 2 forces the form: tests at small sizes)
-  return p->opts.conv_tile >= 2 || tiles >= (p->opts.conv_big_min_tiles > 0 ? p->opts.conv_big_min_tiles : 128);
-}
-
-// Which kernel a problem runs on (rn_conv_kernel_id): 0 = 128-row conv_fwd_kernel, 1 = conv_big_kernel, 2 = conv_halo_kernel
-// with 256 x 256 tiles, 3 = conv_halo_kernel with 512 x 128 tiles.
-// A 3x3 / stride 1 launch that qualifies for the 256 x 256 halo tiles runs as 512 x 128 tiles instead when its channel
-// count is a multiple of 128 and the longer patches fit: the same number of tiles and MACs per tile, but a K chunk stages
-// ~117 KB instead of ~171 KB per workgroup (one 8 KB weight piece per tap instead of 16 KB; the patch of 512 consecutive
-// pixels has relatively fewer halo rows).  Measured inside the step on one box (round 4): head-tower launches 564 -> 511 us,
-// class prediction 1460 -> 1333, ResNet stage-3 3x3 (200 tiles) 59.8 -> 56.8, batch-8 towers 157 -> 152.  conv_tile = 2
-// keeps the 256 x 256 form (tests, A/B), and so do the small launches that only run here because a split-K workspace lets
-// every tile be cut along K.
-static int conv_pick(const rn_conv_problem* p) {
-  if (conv_use_big(p)) {
-    if (!conv_halo_shape(p, 256)) return 1;
-    if (p->opts.conv_tile == 0 && p->opts.conv_big_min_tiles == 0) {
-      // (a launch of fewer tiles than the 256-row kernels normally take got here through its split-K workspace: every
-      // tile cut along K on the 256 x 256 form)
-      long long tiles256 = 0;
-      for (int i = 0; i < p->num_segments; ++i)
-        tiles256 += rn_cdiv((long long)p->seg[i].N * p->seg[i].Ho * p->seg[i].Wo, 256) * rn_cdiv(seg_cols(p->seg[i]), 256);
-      if (tiles256 < 192) return 2;
-      rn_conv_problem q = *p;
-      q.opts.conv_tile = 3;
-      if (conv_use_halo512(&q)) return 3;
-    }
-    return 2;
-  }
-  return conv_use_halo512(p) ? 3 : 0;
-}
-
-// K step of the 128-row kernel: 64, or 32 when the padded channel count is not a multiple of 64 — and for the shallow
-// layers (K = R S Cin <= 256: ResNet stage 1's 256 -> 64, the first 1x1 of stage 2), which are HBM-bound: four stages of half
-// the size stream better than two or three (profiles/r05_ab/summary.tsv: 256 -> 64 at 160 x 160, batch 32, 133.9 -> 119.3 us;
-// 256 -> 128 194.0 -> 183.0) while every deeper layer loses 10 - 15 % to the second barrier per 16 MFMAs.
-static int conv128_bk(const rn_conv_problem* p) {
-  const int cin = rn_conv_cin_pad(p->seg[0].Cin);
-  if (cin % 64 != 0) return 32;
-  return (long long)p->R * p->S * cin <= 256 ? 32 : 64;
-}
-// Tile shape the 128-row kernel runs a problem with: BN = 64 for Cout <= 64 and for small launches (see
-// rn_conv2d_nhwc_fwd), BK = 64 unless the padded channel count is not a multiple of 64; returns the tile count.
-static int conv128_shape(const rn_conv_problem* p, int* BN_out, int* BK_out) {
-  int BN = rn_conv_cout_pad(seg_cols(p->seg[0])) <= 64 ? 64 : 128;
-  const int BK = conv128_bk(p);
-  if (BN == 128) {
-    long long t128 = 0;
-    for (int i = 0; i < p->num_segments; ++i)
-      t128 += rn_cdiv((long long)p->seg[i].N * p->seg[i].Ho * p->seg[i].Wo, 128) * rn_cdiv(rn_conv_cout_pad(seg_cols(p->seg[i])), 128);
-    if (2 * t128 <= rn_num_cus() && p->opts.conv_tile != 1) BN = 64;   // conv_tile = 1 keeps 128 x 128 (tests)
-  }
-  long long tiles = 0;
-  for (int i = 0; i < p->num_segments; ++i)
-    tiles += rn_cdiv((long long)p->seg[i].N * p->seg[i].Ho * p->seg[i].Wo, 128) * rn_cdiv(rn_conv_cout_pad(seg_cols(p->seg[i])), BN);
-  *BN_out = BN; *BK_out = BK;
-  return tiles > 0x7fffffff ? 0x7fffffff : (int)tiles;
-}
-// Parts every tile of a 128-row launch is cut into along K (1: whole tiles).  Enough parts to put about one workgroup on
-// three of every four compute units (opts.splitk_target_blocks moves the target), at least RN_SPLIT128_MIN_STEPS K steps per part (a
-// part costs a 32 - 64 KB partial tile written and read back and a ~2 us hand-off), at most 8 parts (the last arriver
-// keeps one 16-byte load per part in flight), the slots must fit the workspace and the tiles its 4096 counters.
-#define RN_SPLIT128_MIN_STEPS 4
-static int conv128_split_parts(const rn_conv_problem* p, int tiles, int BN, int BK) {
-  if (!p->splitk_ws || p->opts.conv_tile == 1 || tiles < 1 || tiles > 4096) return 1;
-  int ksteps = 0x7fffffff;   // of the launch's shallowest segment
-  for (int i = 0; i < p->num_segments; ++i) {
-    const int terms = p->seg[i].w_terms > 1 ? p->seg[i].w_terms : 1;
-    const int ks = p->R * p->S * (terms * rn_conv_cin_pad(p->seg[i].Cin) / BK);
-    ksteps = ks < ksteps ? ks : ksteps;
-  }
-  // default target: three quarters of the compute units.  Same-box sweep with the counted-wait K loop, three rounds
-  // (tools/bench_infer.py --split-target): batch-1 serving 1.357 / 1.360 / 1.353 ms at 256 workgroups, 1.322 / 1.310 / 1.318 at
-  // 192, 1.323 / 1.323 / 1.315 at 160; batch 8 within +-0.4 % of each other (fewer, longer parts: less exchange traffic).
-  const int target = p->opts.splitk_target_blocks > 0 ? p->opts.splitk_target_blocks : rn_num_cus() * 3 / 4;
-  int S = target / tiles;
-  if (S > ksteps / RN_SPLIT128_MIN_STEPS) S = ksteps / RN_SPLIT128_MIN_STEPS;
-  if (S > 8) S = 8;
-  const long long slot = 128ll * BN * 4;
-  while (S >= 2 && RN_SPLITK_HEADER_BYTES + (long long)tiles * S * slot > p->splitk_ws_bytes) --S;
-  return S >= 2 ? S : 1;
-}
-
-// Balanced tiles for conv_big_kernel's HBM-bound 1x1 launches.  The persistent grid walks its 256-row tiles in rounds of one
-// per workgroup; a launch of 3.1 rounds runs as 4 with most of the chip idle in the last one (ResNet stage 3 `*_out` at
-// B = 32: 800 tiles on 256 workgroups), and a tile's time there is set by its bytes, not by its MFMAs (four to sixteen K
-// steps between a pipeline refill and a 128 KB epilogue).  A 1x1 tile's rows are independent, so the SAME number of rounds
-// can be cut finer: rows = ceil(M / floor(rounds * grid / column tiles)) pixels per tile instead of 256 — every workgroup
-// then walks `rounds` tiles of rows/256 of the bytes each (the rows a tile does not cover are masked: zero-filled by the
-// DMA, never stored; their MFMAs run on zeros).  The busiest workgroup of the 256-row plan keeps its tile count and moves
-// fewer bytes; nobody moves more.  Single-segment 1x1 / stride 1 launches only, shallow enough that bytes set the pace
-// (K <= 512), and only when it shortens the tiles by 8 % or more; opts.conv_tile / conv_big_min_tiles / max_workgroups
-// (tests, A/B) keep whole tiles.  Results are the same values: a tile's accumulation order does not depend on its rows.
-// Returns the rows per tile, 0 = whole 256-row tiles.  The fused BatchNorm partial sums are still written per (tile,
-// half): rn_conv_bn_row_blocks() tells how many 128-row blocks a segment writes.
-static int conv_big_balanced_rows(const rn_conv_problem* p) {
-  if (p->num_segments != 1 || p->R != 1 || p->S != 1 || p->stride_h != 1 || p->stride_w != 1) return 0;
-  if (p->opts.conv_tile || p->opts.conv_big_min_tiles || p->opts.max_workgroups || p->splitk_ws) return 0;
-  const rn_conv_segment& s = p->seg[0];
-  const int terms = s.w_terms > 1 ? s.w_terms : 1;
-  if (terms * rn_conv_cin_pad(s.Cin) > 512) return 0;
-  const long long M = (long long)s.N * s.Ho * s.Wo;
-  const int n_tiles = (int)rn_cdiv(rn_conv_cout_pad(seg_cols(s)), 256);
-  const int G = rn_persistent_grid(0x7fffffff, rn_num_cus(), p->opts);
-  const long long T = rn_cdiv(M, 256) * n_tiles;
-  if (T <= 0 || G <= 0) return 0;
-  const long long rounds = rn_cdiv(T, G);
-  const long long m_tiles = rounds * G / n_tiles;   // row blocks that fit `rounds` rounds
-  if (m_tiles < 1) return 0;
-  long long rows = rn_cdiv(M, m_tiles);
-  rows = (rows + 3) / 4 * 4;
-  if (rows < 64 || rows > 236) return 0;            // (236 = 0.92 * 256)
-  return (int)rows;
-}
-
-int rn_splitk_plan(ConvArgs& a, int min_chunks, void* ws, long long ws_bytes, const rn_launch_opts& opts) {
-  const int total = a.total_tiles;
-  a.split_f = total; a.split_s = 1; a.vtotal = total; a.pad2_ = 0; a.ws = nullptr;
-  const int G0 = rn_persistent_grid(0x7fffffff, rn_num_cus(), opts);
-  const int L = total % G0;
-  int S = ws ? splitk_parts(total, min_chunks, G0, nullptr) : 1;
-  while (S >= 2 && RN_SPLITK_HEADER_BYTES + (long long)L * S * RN_SPLITK_SLOT_BYTES > ws_bytes) --S;
-  if (S < 2) return total < G0 ? total : G0;
-  a.split_f = total - L; a.split_s = S; a.vtotal = L * S; a.ws = (float*)ws;   // vtotal: units of the SPLIT launch
-  return a.split_f ? G0 : L * S;
-}
-
-// K chunks (32 input channels x all taps) of the launch's shortest tile
-static int conv_min_chunks(const rn_conv_problem* p) {
-  int mc = 0x7fffffff;
-  for (int i = 0; i < p->num_segments; ++i) {
-    const int terms = p->seg[i].w_terms > 1 ? p->seg[i].w_terms : 1;
-    const int ch = terms * rn_conv_cin_pad(p->seg[i].Cin) / 32;
-    mc = ch < mc ? ch : mc;
-  }
-  return mc;
-}
-// ... or 0 when this launch cannot split (conv_big_kernel: whole tiles only — its 1x1 layers are HBM-bound)
-static int conv_splitk_min_chunks(const rn_conv_problem* p) { return conv_pick(p) == 2 ? conv_min_chunks(p) : 0; }
-
-// what any problem can use on any grid: 16 KB header + 256 accumulator slots (one per part: L * S <= 256 workgroups)
-extern "C" size_t rn_conv_splitk_workspace_max_bytes(void) { return RN_SPLITK_HEADER_BYTES + 256ull * RN_SPLITK_SLOT_BYTES; }
-
-extern "C" size_t rn_conv_splitk_workspace_bytes(const rn_conv_problem* p) {
-  if (!p || p->num_segments < 1 || p->num_segments > RN_CONV_MAX_SEGMENTS) return 0;
-  if (conv_pick(p) == 0) {   // 128-row kernel: every tile cut into S parts of one [128][BN] fp32 slot each
-    int BN, BK;
-    const int tiles = conv128_shape(p, &BN, &BK);
-    rn_conv_problem q = *p;
-    if (!q.splitk_ws) { q.splitk_ws = (void*)16; q.splitk_ws_bytes = (long long)rn_conv_splitk_workspace_max_bytes(); }   // "if one were attached"
-    const int S = conv128_split_parts(&q, tiles, BN, BK);
-    return S >= 2 ? (size_t)(RN_SPLITK_HEADER_BYTES + (long long)tiles * S * 128 * BN * 4) : 0;
-  }
-  const int mc = conv_splitk_min_chunks(p);
-  if (!mc) return 0;
-  long long tiles = 0;
-  for (int i = 0; i < p->num_segments; ++i) {
-    const rn_conv_segment& s = p->seg[i];
-    tiles += rn_cdiv((long long)s.N * s.Ho * s.Wo, 256) * rn_cdiv(rn_conv_cout_pad(seg_cols(s)), 256);
-  }
-  long long bytes = 0;
-  splitk_parts((int)tiles, mc, rn_persistent_grid(0x7fffffff, rn_num_cus(), p->opts), &bytes);
-  return (size_t)bytes;
-}
-
-/* 0: 128-row kernel, 1: conv_big_kernel, 2: conv_halo_kernel */
-extern "C" int rn_conv_kernel_id(const rn_conv_problem* p) {
-  if (!p || p->num_segments < 1 || p->num_segments > RN_CONV_MAX_SEGMENTS) return -1;
-  return conv_pick(p);
-}
-
-extern "C" int rn_conv_bn_row_blocks(const rn_conv_problem* p, int segment) {
-  if (!p || p->num_segments < 1 || p->num_segments > RN_CONV_MAX_SEGMENTS || segment < 0 || segment >= p->num_segments) return 0;
-  const int kid = conv_pick(p);
-  const long long M = (long long)p->seg[segment].N * p->seg[segment].Ho * p->seg[segment].Wo;
-  if (kid == 1) {
-    const int r = conv_big_balanced_rows(p);
-    if (r) return (int)(2 * rn_cdiv(M, r));
-  }
-  const int rows = kid == 3 ? 512 : (kid ? 256 : 128);
-  return (int)((rows / 128) * rn_cdiv(M, rows));
-}
-
-extern "C" int rn_conv_tile_rows(const rn_conv_problem* p) {
-  if (!p || p->num_segments < 1 || p->num_segments > RN_CONV_MAX_SEGMENTS) return 0;
-  const int kid = conv_pick(p);
-  return kid == 3 ? 512 : (kid ? 256 : 128);
-}
-
-extern "C" int rn_conv2d_nhwc_fwd(const rn_conv_problem* p, void* stream) {
-  RN_CHECK_ARG(p != nullptr, "rn_conv2d_nhwc_fwd: null problem");
-  RN_CHECK_ARG(p->num_segments >= 1 && p->num_segments <= RN_CONV_MAX_SEGMENTS,
-               "rn_conv2d_nhwc_fwd: num_segments=%d", p->num_segments);
-  RN_CHECK_ARG(p->R >= 1 && p->S >= 1 && p->R * p->S <= 32, "rn_conv2d_nhwc_fwd: R*S=%d > 32", p->R * p->S);
-  RN_CHECK_ARG(p->stride_h >= 1 && p->stride_w >= 1, "rn_conv2d_nhwc_fwd: bad stride");
-  RN_CHECK_ARG(p->out_dtype == RN_DT_BF16 || p->out_dtype == RN_DT_F32, "rn_conv2d_nhwc_fwd: bad out_dtype");
-  if (const int orc = rn_validate_launch_opts(p->opts, "rn_conv2d_nhwc_fwd")) return orc;
-  ConvArgs a;
-  a.R = p->R; a.S = p->S; a.sh = p->stride_h; a.sw = p->stride_w; a.pt = p->pad_top; a.pl = p->pad_left;
-  a.act = p->act; a.nseg = p->num_segments; a.pad_ = 0;
-  const int cout_pad0 = rn_conv_cout_pad(seg_cols(p->seg[0]));
-  int BN = cout_pad0 <= 64 ? 64 : 128;
-  // K step: 64 unless the (padded) channel count is small; Cin need only be a multiple of 8 — the
-  // tail of the last K step reads past the pixel's channels (or out of range -> zeros) and meets the
-  // zero-padded weight columns, so it contributes nothing.
-  const int BK = conv128_bk(p);
-  const int kid = conv_pick(p);
-  const bool big = kid == 1 || kid == 2;
-  const bool halo512 = kid == 3;   // 512 x 128 tiles of the halo kernel
-  const int BM = big ? 256 : (halo512 ? 512 : 128);
-  if (!big && !halo512) {
-    // Small launches (batch-8 inference, ResNet stage 4: 100 tiles of 128 x 128 on 256 CUs): 128 x 64 tiles put the work
-    // on twice as many CUs and read 12 KB instead of 16 KB of LDS fragments per wave and K step — the 128-row kernel is
-    // bound by fragment bandwidth at one workgroup per CU (DESIGN.md section 4, round-3 probes).  Only while the
-    // narrower tiles still fit one per CU: at two per CU they share that bandwidth again.  (conv128_shape)
-    int bk_;
-    conv128_shape(p, &BN, &bk_);
-  }
-  const int BNT = big ? 256 : BN;   // n-tile width
-  const int bal_rows = kid == 1 ? conv_big_balanced_rows(p) : 0;
-  int tiles = 0;
-  // conv_big_kernel launch whose segments are all one column tile wide but differ 2x or more in K depth (the FPN lateral 1x1
-  // convs: 512 / 1024 / 2048 input channels): tiles numbered deepest segment first and dealt to the workgroups round-robin
-  // (identity numbering) instead of in the XCD-contiguous ranges that keep neighbouring column tiles on one L2 — there are
-  // no neighbouring column tiles here, and a contiguous range hands one XCD all of the 64-step tiles (181 K steps per CU
-  // there against 87 on average).  The order is internal to the launch: every tile's result is what it was.
-  int order[RN_CONV_MAX_SEGMENTS];
-  for (int i = 0; i < p->num_segments; ++i) order[i] = i;
-  bool deal = false;
-  if (kid == 1 && p->num_segments > 1) {
-    long long dmin = 1ll << 60, dmax = 0;
-    bool one_col = true;
-    for (int i = 0; i < p->num_segments; ++i) {
-      const long long depth = (long long)p->R * p->S * rn_conv_cin_pad(p->seg[i].Cin) * (p->seg[i].w_terms > 1 ? p->seg[i].w_terms : 1);
-      dmin = depth < dmin ? depth : dmin;
-      dmax = depth > dmax ? depth : dmax;
-      one_col = one_col && rn_conv_cout_pad(seg_cols(p->seg[i])) <= 256;
-    }
-    deal = one_col && dmax >= 2 * dmin;
-    if (deal)
-      std::stable_sort(order, order + p->num_segments, [&](int x, int y) {
-        return rn_conv_cin_pad(p->seg[x].Cin) * (p->seg[x].w_terms > 1 ? p->seg[x].w_terms : 1) >
-               rn_conv_cin_pad(p->seg[y].Cin) * (p->seg[y].w_terms > 1 ? p->seg[y].w_terms : 1);
-      });
-  }
-  for (int ii = 0; ii < p->num_segments; ++ii) {
-    const int i = order[ii];
-    const rn_conv_segment& s = p->seg[i];
-    RN_CHECK_ARG(s.x && s.w && s.y, "rn_conv2d_nhwc_fwd: segment %d has a null tensor", i);
-    RN_CHECK_ARG(s.N > 0 && s.H > 0 && s.W > 0 && s.Ho > 0 && s.Wo > 0 && s.Cout > 0 && s.Cin > 0,
-                 "rn_conv2d_nhwc_fwd: segment %d bad shape", i);
-    RN_CHECK_ARG(s.Cin % 8 == 0 && rn_conv_cin_pad(s.Cin) % BK == 0,
-                 "rn_conv2d_nhwc_fwd: segment %d Cin=%d must be a multiple of 8 (K step %d)", i, s.Cin, BK);
-    RN_CHECK_ARG(s.pix_stride % 4 == 0 && s.pix_stride > 0,
-                 "rn_conv2d_nhwc_fwd: segment %d pix_stride=%d must be a positive multiple of 4", i, s.pix_stride);
-    RN_CHECK_ARG(s.Cout % 4 == 0, "rn_conv2d_nhwc_fwd: segment %d Cout=%d not a multiple of 4", i, s.Cout);
-    const int cp = rn_conv_cout_pad(seg_cols(s));
-    RN_CHECK_ARG((cp <= 64) == (cout_pad0 <= 64), "rn_conv2d_nhwc_fwd: segments mix Cout tile widths");
-    RN_CHECK_ARG(!s.w_pair || ((big || halo512) && p->out_dtype == RN_DT_F32 && s.w_terms <= 1 && !s.scale && !s.shift &&
-                               !s.residual && !s.bn_partial),
-                 "rn_conv2d_nhwc_fwd: segment %d: w_pair needs an f32 launch without scale / shift / residual that the 256- / "
-                 "512-row kernels take (rn_conv_kernel_id() != 0)", i);
-    RN_CHECK_ARG(((uintptr_t)s.x | (uintptr_t)s.w | (uintptr_t)s.y | (uintptr_t)s.residual) % 16 == 0,
-                 "rn_conv2d_nhwc_fwd: segment %d tensors must be 16-byte aligned", i);
-    const long long M = (long long)s.N * s.Ho * s.Wo;
-    RN_CHECK_ARG(M < (1ll << 31) && (long long)s.N * s.H * s.W * s.pix_stride * 2 < (1ll << 31),
-                 "rn_conv2d_nhwc_fwd: segment %d input exceeds the 2 GiB buffer-addressing limit", i);
-    // the last input row/col a valid tap may touch must be inside the image
-    ConvSegDev& d = a.seg[ii];
-    d.x = (const uint16_t*)s.x; d.w = (const uint16_t*)s.w; d.y = s.y;
-    d.scale = s.scale; d.shift = s.shift; d.residual = (const uint16_t*)s.residual;
-    d.bn_partial = s.bn_partial;
-    d.bn_y = (const uint16_t*)s.bn_bwd_y;
-    d.bn_fwd = s.bn_bwd_fwd;
-    if (s.bn_bwd_y) {
-      RN_CHECK_ARG(s.bn_partial && s.bn_bwd_fwd && p->out_dtype == RN_DT_BF16 && !s.scale && !s.shift && !s.bias &&
-                       !s.residual && p->act == RN_ACT_NONE && s.Cout % 8 == 0 && (uintptr_t)s.bn_bwd_y % 16 == 0,
-                   "rn_conv2d_nhwc_fwd: segment %d: bn_bwd_y needs bn_partial + bn_bwd_fwd on a plain bf16 launch", i);
-    }
-    RN_CHECK_ARG((s.bn_bwd_y != nullptr) == (p->seg[0].bn_bwd_y != nullptr),
-                 "rn_conv2d_nhwc_fwd: bn_bwd_y must be set on all segments or none");
-    d.bias = s.bias;
-    d.N = s.N; d.H = s.H; d.W = s.W; d.Cin = s.Cin; d.pix_stride = s.pix_stride;
-    d.Ho = s.Ho; d.Wo = s.Wo; d.Cout = seg_cols(s);
-    d.pair_cout = s.w_pair ? s.Cout : 0;
-    d.rows = kid == 1 ? bal_rows : 0;   // conv_big_kernel: balanced tiles (single-segment launches only)
-    d.M = (int)M;
-    d.tile_begin = tiles;
-    d.n_tiles = (int)rn_cdiv(cp, BNT);
-    const int terms = s.w_terms > 1 ? s.w_terms : 1;
-    RN_CHECK_ARG(terms <= 3, "rn_conv2d_nhwc_fwd: segment %d w_terms=%d (1..3)", i, s.w_terms);
-    d.cwrap = rn_conv_cin_pad(s.Cin);
-    d.CinP = terms * d.cwrap;
-    d.halo_pitch = s.W + 1;
-    if (rn_conv_halo_patch_pixels(s.N, s.H, s.W, rn_conv_halo_pitch(s.W), halo512 ? 512 : 256) <= rn_conv_halo_capacity(halo512 ? 512 : 256))
-      d.halo_pitch = rn_conv_halo_pitch(s.W);
-    tiles += (int)rn_cdiv(M, d.rows ? d.rows : BM) * d.n_tiles;
-  }
-  a.total_tiles = tiles;
-  a.split_f = a.vtotal = tiles; a.split_s = 1; a.pad2_ = 0; a.ws = nullptr;
-  RN_CHECK_ARG(p->splitk_ws == nullptr || ((uintptr_t)p->splitk_ws % 16 == 0 && p->splitk_ws_bytes >= 0),
-               "rn_conv2d_nhwc_fwd: splitk_ws must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const bool f32 = p->out_dtype == RN_DT_F32;
-  if (halo512) return rn_launch_conv_halo(a, f32, p->opts, st, 4);
-  if (kid == 2) {
-    rn_splitk_plan(a, conv_splitk_min_chunks(p), p->splitk_ws, p->splitk_ws_bytes, p->opts);
-    return rn_launch_conv_halo(a, f32, p->opts, st);
-  }
-  if (big) {
-    a.pad_ = 1;   // bit 0: float-reciprocal index arithmetic in the tile set-up, valid while every M < 2^22
-    for (int i = 0; i < a.nseg; ++i)
-      if (a.seg[i].M >= (1 << 22)) a.pad_ = 0;
-    if (deal) a.pad_ |= 2;   // bit 1: tiles dealt round-robin (see above)
-    return rn_launch_conv_big(a, f32, p->opts, st);
-  }
-  a.pad_ = 1;   // bit 0: float-reciprocal index arithmetic in the prologue, valid while every M < 2^22
-  for (int i = 0; i < a.nseg; ++i)
-    if (a.seg[i].M >= (1 << 22)) a.pad_ = 0;
-  // 128-row kernel.  With a split-K workspace a SMALL launch of a deep layer (fewer tiles than the chip has compute units:
-  // batch-1 / batch-8 inference, ResNet stage 3 / 4, the FPN laterals) cuts every tile along K (conv128_split_parts).
-  const int S128 = conv128_split_parts(p, tiles, BN, BK);
-  if (S128 >= 2) {
-    a.split_s = S128; a.vtotal = tiles * S128; a.ws = (float*)p->splitk_ws;
-    return launch_conv128<true>(a, BN, BK, f32, st);
-  }
-  return launch_conv128<false>(a, BN, BK, f32, st);
+int rn_launch_conv128(const ConvArgs& a, int BN, int BK, bool f32, bool split, hipStream_t st) {
+  return split ? launch_conv128<true>(a, BN, BK, f32, st) : launch_conv128<false>(a, BN, BK, f32, st);
 }
 
 // ---- weight / input packing ----------------------------------------------------------------

@@ -1,5 +1,5 @@
 // rn_conv_dev.h — device-side declarations shared by the implicit-GEMM conv kernels
-// (rn_conv.hip: 128-row tiles; rn_conv_big.hip: 256 x 256 tiles).
+// (rn_conv.hip: 128-row tiles; rn_conv_big.hip: 256 x 256 tiles) and their host-side dispatcher (rn_conv_dispatch.hip).
 #ifndef RN_CONV_DEV_H_
 #define RN_CONV_DEV_H_
 #include "rn_common.h"
@@ -27,7 +27,7 @@ struct ConvSegDev {
   int pair_cout, rows;               // rn_conv_segment.w_pair: Cout above = the GEMM's columns (rn_conv_pair_rows), this =
                                      // the channels of y / bias; 0 = off (256- / 512-row kernels, f32 epilogue only)
                                      // rows (conv_big_kernel): output pixels a tile really covers, 0 = all 256 — balanced
-                                     // tiles of the HBM-bound 1x1 layers (rn_conv.hip: conv_big_balanced_rows)
+                                     // tiles of the HBM-bound 1x1 layers (rn_conv_dispatch.hip: conv_big_balanced_rows)
 };
 
 
@@ -68,13 +68,14 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds_wav
 #define RN_OOB 0x80000000u
 
 
+// The launch points of the three kernel families; rn_conv_dispatch.hip (conv_plan) decides which one a problem gets and
+// fills the ConvArgs.
+// rn_conv.hip: the 128-row kernel with 128 x BN x BK tiles; split: every tile cut along K into a.split_s parts
+int rn_launch_conv128(const ConvArgs& a, int BN, int BK, bool f32, bool split, hipStream_t st);
 // rn_conv_big.hip
 int rn_launch_conv_big(const ConvArgs& a, bool out_f32, const rn_launch_opts& opts, hipStream_t st);   // (bn_y set on segment 0: the BN_BWD variant)
 // rn_conv_halo.hip (3x3 / stride 1 / pad 1)
 int rn_launch_conv_halo(const ConvArgs& a, bool out_f32, const rn_launch_opts& opts, hipStream_t st, int wm = 2);   // wm = 4: 512 x 128 tiles
-// plan of the last-round split for a persistent launch of `total_tiles` tiles whose shortest tile has `min_chunks`
-// K chunks; fills a.split_f / split_s / vtotal / ws (no split when ws is null or too small) and returns the grid
-int rn_splitk_plan(ConvArgs& a, int min_chunks, void* ws, long long ws_bytes, const rn_launch_opts& opts);
 int rn_conv_halo_patch_pixels(int N, int H, int W, int pitch, int BM = 256);
 int rn_conv_halo_pitch(int W);
 int rn_conv_halo_capacity(int BM = 256);

@@ -4,6 +4,8 @@ MI355X's 256 compute units).  Pins which kernel family, tile shape and split pla
 get — the policy DESIGN.md section 4 describes — so that a dispatcher edit shows up as a diff here, not as a silent
 slow-down on the GPU box."""
 import ctypes
+import json
+import os
 
 import pytest
 
@@ -96,6 +98,41 @@ def test_forced_tile_shapes_keep_whole_tiles():
     p.opts = _C.LaunchOpts(max_workgroups=64)
     assert _q(p)[2] == 400
 
+
+
+def _table():
+    with open(os.path.join(os.path.dirname(__file__), "golden", "conv_dispatch_table.json")) as f:
+        return json.load(f)["rows"]
+
+
+def test_dispatch_table():
+    """The whole policy, not only the bench layers: tests/golden/conv_dispatch_table.json holds (descriptor, kernel id, tile
+    rows, BatchNorm row blocks per segment, split-K workspace bytes) as the dispatcher answered BEFORE its decisions moved
+    into one plan (rn_conv_dispatch.hip: conv_plan) — recorded from that library, 256 compute units, never from the
+    planner.  The rows are one or two descriptors of every distinct outcome (kernel id x tile rows x splits or not x balanced
+    or not x forced rn_launch_opts) of a grid of 610 984 descriptors, and of every such outcome with each batch (1 / 2 / 8 /
+    32), shape (the pyramid sizes, odd and wide ones, one of more than 2^22 pixels), 1x1 / 3x3, stride 1 / 2, output type with
+    w_terms / w_pair, workspace (none / 64 MB / 1 MB), bias + residual, and segment count (1, 2, 3, the five-level and
+    ten-segment launches).  The library must reproduce every row."""
+    lib = _C.lib()
+    rows = _table()
+    assert 300 <= len(rows) <= 2500
+    assert {r[10] for r in rows} == {0, 1, 2, 3}
+    bad = []
+    for B, k, stride, segs, f32, w_terms, w_pair, ws_bytes, opts, bias_res, kid, tile_rows, blocks, ws in rows:
+        p = _problem(B, 0, 0, 0, 0, k, stride=stride, f32=bool(f32), w_terms=w_terms, w_pair=w_pair, segs=[tuple(s) for s in segs])
+        p.opts = _C.LaunchOpts(**opts)
+        if ws_bytes:
+            p.splitk_ws, p.splitk_ws_bytes = 16, ws_bytes
+        for i in range(len(segs)):
+            if bias_res:   # read as "null or not" only
+                p.seg[i].bias, p.seg[i].residual = 16, 16
+        r = ctypes.byref(p)
+        got = [lib.rn_conv_kernel_id(r), lib.rn_conv_tile_rows(r), [lib.rn_conv_bn_row_blocks(r, i) for i in range(len(segs))],
+               int(lib.rn_conv_splitk_workspace_bytes(r))]
+        if got != [kid, tile_rows, blocks, ws]:
+            bad.append((B, k, stride, segs, f32, w_terms, w_pair, ws_bytes, opts, bias_res, got, [kid, tile_rows, blocks, ws]))
+    assert not bad, (len(bad), bad[:5])
 
 def _bn_problem(segs):
     p = _C.BnProblem()

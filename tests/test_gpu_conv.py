@@ -400,7 +400,7 @@ BALANCED_CASES = [
 
 @pytest.mark.parametrize("case", BALANCED_CASES, ids=["x".join(str(v) for v in c) for c in BALANCED_CASES])
 def test_conv_big_balanced_tiles(cuda, case):
-    """conv_big_kernel's balanced tiles (rn_conv.hip: conv_big_balanced_rows): an HBM-bound 1x1 launch whose 256-row tiles
+    """conv_big_kernel's balanced tiles (rn_conv_dispatch.hip: conv_big_balanced_rows): an HBM-bound 1x1 launch whose 256-row tiles
     would leave the last round of the persistent grid mostly idle runs the same number of rounds with tiles of fewer rows.
     Same values as whole tiles (forced with conv_tile = 2); the fused BatchNorm partial sums come as two blocks per tile
     (rn_conv_bn_row_blocks) and add up to the sums over the stored tensor."""
