@@ -398,7 +398,9 @@ typedef struct {
 size_t rn_wgrad_workspace_bytes(const rn_wgrad_problem* problem /* host */);
 /* Which kernel rn_conv2d_nhwc_wgrad runs for `problem`: 0 = wgrad_kernel (128 x 128 per-tap tiles, K step 64 pixels),
  * 1 = wgrad_big_kernel (256 x 256 per-tap tiles, ping-pong), 2 = wgrad_halo_kernel (3x3 / stride 1 / pad 1: all nine taps
- * in one workgroup, reduction over image rows); -1 on a malformed problem.  Bench bookkeeping only. */
+ * in one workgroup, reduction over image rows); -1 on a malformed problem.
+ * The queries here and below and the two launch functions read ONE host-side plan of the call (rn_wgrad_dispatch.hip): the
+ * kernel a query names and the workspace it sizes are the ones the launch uses. */
 int rn_wgrad_kernel_id(const rn_wgrad_problem* problem /* host */);
 int rn_conv2d_nhwc_wgrad(const rn_wgrad_problem* problem /* host */, float* dw, float beta, void* workspace,
                          size_t workspace_bytes, void* stream);
@@ -406,7 +408,8 @@ int rn_conv2d_nhwc_wgrad(const rn_wgrad_problem* problem /* host */, float* dw, 
  * host arrays).  Layers of IDENTICAL geometry that wgrad_halo_kernel serves (n <= 8: the eight head-tower layers, the 3x3
  * layers of one ResNet stage) run as ONE launch over (layer, co tile, ci tile) tiles + one reduction launch: a split-K
  * workgroup writes its whole 288 KB accumulator as a partial tile, so a launch costs ~75 MB of partials however small
- * the layer, and a grouped launch needs 1/n of the pixel chunks per layer.  rn_wgrad_group_fused tells which way a group
+ * the layer, and a grouped launch needs 1/n of the pixel chunks per layer.  Identical one-segment layers it does not
+ * serve run as the segments of one merged launch of the per-tap kernels.  rn_wgrad_group_fused tells which way a group
  * goes (1: one launch); other groups are issued layer by layer.  Deterministic either way. */
 size_t rn_wgrad_group_workspace_bytes(const rn_wgrad_problem* const* problems /* host */, int n);
 int rn_wgrad_group_fused(const rn_wgrad_problem* const* problems /* host */, int n);

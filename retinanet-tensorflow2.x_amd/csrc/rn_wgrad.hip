@@ -18,8 +18,6 @@
 //     partial tile to the workspace, a second kernel adds the chunks in index order
 //     (deterministic; no float atomics).
 // MFMA-bound for large layers; the partial-tile traffic is chunks * |W| * 4 B.
-#include <string.h>
-
 #include "rn_wgrad_dev.h"
 
 __device__ __forceinline__ void wg_dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, unsigned voff) {
@@ -335,257 +333,24 @@ wgrad_reduce_kernel(const float4* __restrict__ ws_all, long long n4, int chunks,
   }
 }
 
-// workgroups a launch aims for (2 per CU x 256 CUs); fewer = fewer split-K partials to write and reduce, more = better
-// balance.  Tunable per call (rn_launch_opts.wgrad_target_blocks) for A/B timing.
-// (rn_launch_opts.wgrad_target_blocks overrides it, .wgrad_kernel picks the kernel family.)
-
-static int wgrad_plan(const rn_wgrad_problem* p, WgArgs& a) {
-  if (!p || p->num_segments < 1 || p->num_segments > RN_CONV_MAX_SEGMENTS) return -1;
-  if (p->R < 1 || p->S < 1 || p->stride_h < 1 || p->stride_w < 1) return -1;
-  if (rn_validate_launch_opts(p->opts, "rn_conv2d_nhwc_wgrad")) return -1;
-  a.R = p->R; a.S = p->S; a.sh = p->stride_h; a.sw = p->stride_w; a.pt = p->pad_top; a.pl = p->pad_left;
-  a.nseg = p->num_segments;
-  a.Cin = p->seg[0].Cin; a.Cout = p->seg[0].Cout;
-  if (a.Cin % 8 || a.Cout % 4 || a.Cin <= 0 || a.Cout <= 0) return -1;
-  a.co_tiles = (int)rn_cdiv(a.Cout, 128);
-  a.ci_tiles = (int)rn_cdiv(a.Cin, 128);
-  long long Ptot = 0;
-  for (int i = 0; i < p->num_segments; ++i) {
-    const rn_wgrad_segment& s = p->seg[i];
-    if (!s.x || !s.dy || s.Cin != a.Cin || s.Cout != a.Cout) return -1;
-    const long long P = (long long)s.N * s.Ho * s.Wo;
-    if (P <= 0 || P >= (1ll << 24)) return -1;
-    const long long dyS = s.dy_pix_stride > 0 ? s.dy_pix_stride : s.Cout;
-    if (dyS < s.Cout || (dyS % 4)) return -1;
-    const long long xS = s.x_pix_stride > 0 ? s.x_pix_stride : s.Cin;
-    if (xS % 4) return -1;
-    if ((long long)s.N * s.H * s.W * xS * 2 >= (1ll << 31) || P * dyS * 2 >= (1ll << 31)) return -1;
-    if ((long long)s.N * s.H * s.W >= (1ll << 24) || xS >= (1 << 24) || dyS >= (1 << 24)) return -1;   // 24-bit multiplies
-    Ptot += P;
-  }
-  const int tiles = a.co_tiles * a.ci_tiles * a.R * a.S;
-  a.co_groups = (int)rn_cdiv(tiles, 64);
-  if (a.co_groups > a.co_tiles) a.co_groups = a.co_tiles;
-  a.gco = (int)rn_cdiv(a.co_tiles, a.co_groups);
-  a.co_groups = (int)rn_cdiv(a.co_tiles, a.gco);
-  // 512 = one round of two workgroups per CU: measured (tools/bench_wgrad.py, same process) 58 vs 75 us on the 128 <-> 512
-  // 1x1 layers of ResNet stage 2 and 41 vs 55 us on 2048 -> 512 against the former 1024 — these layers are HBM-bound and
-  // every extra pixel chunk is another |W| x 4 bytes of partial tile written and read back
-  long long target = rn_cdiv(p->opts.wgrad_target_blocks > 0 ? p->opts.wgrad_target_blocks : 512, tiles);
-  if (target < 1) target = 1;
-  if (target > 256) target = 256;
-  long long CH = rn_cdiv(rn_cdiv(Ptot, target), WG_BK) * WG_BK;
-  if (CH < WG_BK) CH = WG_BK;
-  a.CH = (int)CH;
-  int chunks = 0;
-  for (int i = 0; i < p->num_segments; ++i) {
-    const rn_wgrad_segment& s = p->seg[i];
-    WgSegDev& d = a.seg[i];
-    d.x = (const uint16_t*)s.x; d.dy = (const uint16_t*)s.dy;
-    d.N = s.N; d.H = s.H; d.W = s.W; d.Ho = s.Ho; d.Wo = s.Wo;
-    d.P = s.N * s.Ho * s.Wo;
-    d.chunk_begin = chunks;
-    d.dyS = s.dy_pix_stride > 0 ? s.dy_pix_stride : s.Cout;
-    d.xS = s.x_pix_stride > 0 ? s.x_pix_stride : s.Cin;
-    d.pad_ = 0;
-    chunks += (int)rn_cdiv(d.P, CH);
-  }
-  a.total_chunks = chunks;
-  a.pad_ = 0;
-  // large layers: 256 x 256 per-tap tiles on the ping-pong kernel (rn_wgrad_big.hip); pad_ = 1 marks the choice
-  if (p->opts.wgrad_kernel != 1 && rn_wgrad_big_plan(p, a)) a.pad_ = 1;
-  return 0;
-}
-
-/* which kernel rn_conv2d_nhwc_wgrad runs for `problem`: 0 = wgrad_kernel (128 x 128 per-tap tiles), 1 = wgrad_big_kernel
- * (256 x 256 per-tap tiles), 2 = wgrad_halo_kernel (3x3 / stride 1: all nine taps per workgroup); -1 on a malformed
- * problem.  Profiling / bench bookkeeping only. */
-extern "C" int rn_wgrad_kernel_id(const rn_wgrad_problem* p) {
-  WgArgs a;
-  if (wgrad_plan(p, a)) return -1;
-  WhArgs h;
-  if (rn_wgrad_halo_plan(&p, 1, h)) return 2;
-  return a.pad_;
-}
-
-extern "C" size_t rn_wgrad_workspace_bytes(const rn_wgrad_problem* p) {
-  WgArgs a;
-  if (wgrad_plan(p, a)) return 0;
-  WhArgs h;
-  if (rn_wgrad_halo_plan(&p, 1, h)) return rn_wgrad_halo_workspace_bytes(h);
-  return (size_t)a.total_chunks * a.Cout * a.R * a.S * a.Cin * sizeof(float);
-}
-
-// partial-tile launch of a planned problem (wgrad_big_kernel or wgrad_kernel) + the ordered reduction.  ngroups > 1: the
-// problem's segments are LAYERS of a grouped call (one segment each, equal chunk counts): segment g's partial tiles are the
-// chunks [g * total_chunks / ngroups, ...) of the workspace and its sum goes to dws.p[g].
-static int wgrad_launch_planned(WgArgs& a, const rn_launch_opts& opts, void* workspace, hipStream_t st, const WgDwPtrs& dws,
-                                int ngroups, float beta) {
-  a.ws = (float*)workspace;
-  const long long n4 = (long long)a.Cout * a.R * a.S * a.Cin / 4;
-  int blocks = (int)(rn_cdiv(n4, 64) < 4096 ? rn_cdiv(n4, 64) : 4096);
-  if (blocks * ngroups > 8192) blocks = 8192 / ngroups;
-  if (a.pad_ == 1) {
-    const int rc = rn_launch_wgrad_big(a, opts, st);
-    if (rc != RN_OK) return rc;
-  } else {
-    const int lds = 5 * WG_TILE_BYTES;
+int rn_launch_wgrad128(const WgArgs& a, bool linear, unsigned grid, hipStream_t st) {
+  static unsigned long long attr_set = 0;   // one bit per device
+  const int lds = 5 * WG_TILE_BYTES;
+  if (RN_ATTRS_NEEDED(attr_set)) {
     RN_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     RN_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    dim3 grid((unsigned)(a.gco * a.ci_tiles * a.R * a.S * a.co_groups * a.total_chunks));
-    bool linear = a.sh == 1 && a.sw == 1 && a.pt == (a.R - 1) / 2 && a.pl == (a.S - 1) / 2 && (a.R & 1) && (a.S & 1);
-    for (int i = 0; i < a.nseg; ++i) {
-      const WgSegDev& s = a.seg[i];
-      linear = linear && s.Ho == s.H && s.Wo == s.W &&
-               (long long)s.N * s.H * s.W * (s.xS > s.dyS ? s.xS : s.dyS) * 2 < (1ll << 31) - (1ll << 24);
-    }
-    if (linear) hipLaunchKernelGGL(wgrad_kernel<true>, grid, dim3(WG_THREADS), lds, st, a);
-    else hipLaunchKernelGGL(wgrad_kernel<false>, grid, dim3(WG_THREADS), lds, st, a);
-    RN_CHECK_LAUNCH();
+    RN_ATTRS_DONE(attr_set);
   }
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks, ngroups), dim3(256), 0, st, (const float4*)workspace, n4,
-                     a.total_chunks / ngroups, dws, beta);
+  if (linear) hipLaunchKernelGGL(wgrad_kernel<true>, dim3(grid), dim3(WG_THREADS), lds, st, a);
+  else hipLaunchKernelGGL(wgrad_kernel<false>, dim3(grid), dim3(WG_THREADS), lds, st, a);
   RN_CHECK_LAUNCH();
   return RN_OK;
 }
 
-extern "C" int rn_conv2d_nhwc_wgrad(const rn_wgrad_problem* p, float* dw, float beta, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-  WgArgs a;
-  RN_CHECK_ARG(wgrad_plan(p, a) == 0, "rn_conv2d_nhwc_wgrad: bad problem (Cin %% 8, Cout %% 4, < 2^24 pixels, < 2 GiB tensors)");
-  RN_CHECK_ARG(dw != nullptr, "rn_conv2d_nhwc_wgrad: null dw");
-  const size_t need = rn_wgrad_workspace_bytes(p);
-  if (!workspace || workspace_bytes < need) {
-    rn_set_error("rn_conv2d_nhwc_wgrad: workspace %zu < %zu", workspace_bytes, need);
-    return RN_ENOMEM;
-  }
-  {
-    WhArgs h;
-    if (rn_wgrad_halo_plan(&p, 1, h)) {
-      h.ws = (float*)workspace;
-      const int rc = rn_launch_wgrad_halo(h, p->opts, (hipStream_t)stream);
-      if (rc != RN_OK) return rc;
-      const long long nb4 = (long long)h.Cout * 9 * h.Cin / 4;
-      int blocksh = (int)(rn_cdiv(nb4, 64) < 4096 ? rn_cdiv(nb4, 64) : 4096);
-      WgDwPtrs dws;
-      dws.p[0] = (float4*)dw;
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocksh), dim3(256), 0, (hipStream_t)stream, (const float4*)workspace, nb4,
-                         h.total_chunks, dws, beta);
-      RN_CHECK_LAUNCH();
-      return RN_OK;
-    }
-  }
-  WgDwPtrs one;
-  one.p[0] = (float4*)dw;
-  return wgrad_launch_planned(a, p->opts, workspace, (hipStream_t)stream, one, 1, beta);
-}
-
-// ---- several layers of identical geometry in one launch -----------------------------------------------------------
-// Equivalent to n calls of rn_conv2d_nhwc_wgrad.  When the layers share their geometry and wgrad_halo_kernel serves it
-// (the eight head-tower layers, the 3x3 layers of a ResNet stage), they run as ONE launch whose tiles are
-// (layer, co tile, ci tile): the split-K plan then cuts the pixels into 1/n of the chunks per layer — every workgroup
-// writes its whole accumulator (288 KB) as a partial tile, so a launch costs 75 MB of partials however small the layer —
-// and one reduction launch sums all layers.  Anything else falls back to the per-layer calls.
-// Round 6: layers that wgrad_halo_kernel does not serve (the 1x1 layers of a ResNet stage: five / six of identical geometry)
-// group too, WITHOUT another kernel: a layer of one segment becomes a SEGMENT of a merged problem.  The partial-tile kernels
-// already walk per-segment (x, dy) pointers and chunk ranges, and with identical geometry every segment gets the same
-// number of chunks, so segment g's partial tiles are a contiguous [chunks / n] slice of the workspace — exactly the
-// [group][chunk] layout the grouped reduction reads.  Same split-K effect as the halo group: the plan aims for the same
-// number of workgroups over n layers' pixels, i.e. 1/n of the partial tiles per layer, one launch + one reduction for n.
-static bool wgrad_layers_as_segments(const rn_wgrad_problem* const* ps, int n, rn_wgrad_problem& m) {
-  if (!ps || n < 2 || n > RN_WGRAD_MAX_GROUP || n > RN_CONV_MAX_SEGMENTS) return false;
-  const rn_wgrad_problem& p0 = *ps[0];
-  if (p0.num_segments != 1) return false;
-  m = p0;
-  m.num_segments = n;
-  const rn_wgrad_segment& s0 = p0.seg[0];
-  for (int i = 0; i < n; ++i) {
-    const rn_wgrad_problem& q = *ps[i];
-    if (q.num_segments != 1 || q.R != p0.R || q.S != p0.S || q.stride_h != p0.stride_h || q.stride_w != p0.stride_w ||
-        q.pad_top != p0.pad_top || q.pad_left != p0.pad_left || memcmp(&q.opts, &p0.opts, sizeof(rn_launch_opts)) != 0)
-      return false;
-    const rn_wgrad_segment& s = q.seg[0];
-    if (s.N != s0.N || s.H != s0.H || s.W != s0.W || s.Cin != s0.Cin || s.Ho != s0.Ho || s.Wo != s0.Wo || s.Cout != s0.Cout ||
-        s.dy_pix_stride != s0.dy_pix_stride || s.x_pix_stride != s0.x_pix_stride)
-      return false;
-    m.seg[i] = s;
-  }
-  WgArgs a;
-  if (wgrad_plan(&m, a) || a.total_chunks % n) return false;
-  for (int i = 0; i < n; ++i)
-    if (a.seg[i].chunk_begin != i * (a.total_chunks / n)) return false;
-  return true;
-}
-
-extern "C" size_t rn_wgrad_group_workspace_bytes(const rn_wgrad_problem* const* ps, int n) {
-  if (!ps || n < 1) return 0;
-  size_t need = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!ps[i]) return 0;
-    const size_t b = rn_wgrad_workspace_bytes(ps[i]);
-    if (b == 0) return 0;
-    need = b > need ? b : need;
-  }
-  WhArgs h;
-  if (n > 1 && n <= RN_WGRAD_MAX_GROUP && rn_wgrad_halo_plan(ps, n, h)) {
-    const size_t g = rn_wgrad_halo_workspace_bytes(h);
-    need = g > need ? g : need;
-  } else {
-    rn_wgrad_problem m;
-    if (wgrad_layers_as_segments(ps, n, m)) {
-      const size_t g = rn_wgrad_workspace_bytes(&m);
-      need = g > need ? g : need;
-    }
-  }
-  return need;
-}
-
-extern "C" int rn_wgrad_group_fused(const rn_wgrad_problem* const* ps, int n) {   // 1: one grouped launch, 0: per-layer calls
-  if (!ps || n < 2 || n > RN_WGRAD_MAX_GROUP) return 0;
-  for (int i = 0; i < n; ++i)
-    if (!ps[i]) return 0;
-  WhArgs h;
-  if (rn_wgrad_halo_plan(ps, n, h)) return 1;
-  rn_wgrad_problem m;
-  return wgrad_layers_as_segments(ps, n, m) ? 1 : 0;
-}
-
-extern "C" int rn_conv2d_nhwc_wgrad_group(const rn_wgrad_problem* const* ps, int n, float* const* dws, float beta,
-                                          void* workspace, size_t workspace_bytes, void* stream) {
-  RN_CHECK_ARG(ps && dws && n >= 1, "rn_conv2d_nhwc_wgrad_group: bad argument");
-  for (int i = 0; i < n; ++i) RN_CHECK_ARG(ps[i] && dws[i], "rn_conv2d_nhwc_wgrad_group: null problem / output %d", i);
-  const size_t need = rn_wgrad_group_workspace_bytes(ps, n);
-  RN_CHECK_ARG(need > 0, "rn_conv2d_nhwc_wgrad_group: bad problem");
-  if (!workspace || workspace_bytes < need) {
-    rn_set_error("rn_conv2d_nhwc_wgrad_group: workspace %zu < %zu", workspace_bytes, need);
-    return RN_ENOMEM;
-  }
-  WhArgs h;
-  if (n > 1 && n <= RN_WGRAD_MAX_GROUP && rn_wgrad_halo_plan(ps, n, h)) {
-    h.ws = (float*)workspace;
-    const int rc = rn_launch_wgrad_halo(h, ps[0]->opts, (hipStream_t)stream);
-    if (rc != RN_OK) return rc;
-    const long long nb4 = (long long)h.Cout * 9 * h.Cin / 4;
-    int blocks = (int)(rn_cdiv(nb4, 64) < 4096 ? rn_cdiv(nb4, 64) : 4096);
-    if (blocks * n > 8192) blocks = 8192 / n;
-    WgDwPtrs d;
-    for (int i = 0; i < n; ++i) d.p[i] = (float4*)dws[i];
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks, n), dim3(256), 0, (hipStream_t)stream, (const float4*)workspace, nb4,
-                       h.total_chunks, d, beta);
-    RN_CHECK_LAUNCH();
-    return RN_OK;
-  }
-  rn_wgrad_problem m;
-  if (wgrad_layers_as_segments(ps, n, m)) {
-    WgArgs a;
-    RN_CHECK_ARG(wgrad_plan(&m, a) == 0, "rn_conv2d_nhwc_wgrad_group: bad merged problem");
-    WgDwPtrs d;
-    for (int i = 0; i < n; ++i) d.p[i] = (float4*)dws[i];
-    return wgrad_launch_planned(a, m.opts, workspace, (hipStream_t)stream, d, n, beta);
-  }
-  for (int i = 0; i < n; ++i) {
-    const int rc = rn_conv2d_nhwc_wgrad(ps[i], dws[i], beta, workspace, workspace_bytes, stream);
-    if (rc != RN_OK) return rc;
-  }
+int rn_launch_wgrad_reduce(const void* workspace, long long n4, int chunks, const WgDwPtrs& dws, int blocks, int ngroups,
+                           float beta, hipStream_t st) {
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks, ngroups), dim3(256), 0, st, (const float4*)workspace, n4, chunks, dws,
+                     beta);
+  RN_CHECK_LAUNCH();
   return RN_OK;
 }

@@ -16,17 +16,11 @@
 //     out-of-range buffer offset (hardware zero fill).
 // One workgroup = one (co tile, ci tile, tap, pixel chunk); partial tiles go to the same workspace layout as
 // rn_wgrad.hip and are summed by its deterministic reduce kernel.
-#include <algorithm>
-#include <mutex>
-#include <string>
-#include <unordered_map>
-#include <vector>
-
 #include "rn_wgrad_dev.h"
 
 namespace {
 
-constexpr int BK = 32, STAGES = 4;
+constexpr int BK = WGB_BK, STAGES = 4;
 constexpr int OP_BYTES = BK * 512;            // one operand tile: 32 pixel rows x 256 channels bf16
 constexpr int STAGE_BYTES = 2 * OP_BYTES;
 constexpr int LDS_BYTES = STAGES * STAGE_BYTES;
@@ -306,100 +300,7 @@ __global__ void __launch_bounds__(512) wgrad_big_kernel(const WgArgs args) {
 
 }  // namespace
 
-
-// Layers worth the 256 x 256 tile: both channel counts >= 256 and enough pixels to split K over the CUs.
-bool rn_wgrad_big_plan(const rn_wgrad_problem* p, WgArgs& a) {
-  if (a.Cin < 256 || a.Cout < 256) return false;
-  long long Ptot = 0;
-  for (int i = 0; i < p->num_segments; ++i) Ptot += (long long)p->seg[i].N * p->seg[i].Ho * p->seg[i].Wo;
-  const int co_tiles = (int)rn_cdiv(a.Cout, 256), ci_tiles = (int)rn_cdiv(a.Cin, 256);
-  const int tiles = co_tiles * ci_tiles * a.R * a.S;
-  if ((Ptot < 16384 && p->opts.wgrad_kernel < 2) || tiles > 512) return false;
-  a.co_tiles = co_tiles;
-  a.ci_tiles = ci_tiles;
-  a.co_groups = 1;
-  a.gco = co_tiles;
-  // One workgroup per CU (128 KB of LDS).  Candidates: chunk lengths that give about 1, 1.5, 2 and 3 rounds of
-  // the 256 CUs; segments (pyramid levels) are chunked separately, so each candidate grows its chunk until the
-  // workgroup count fits.  The kernel hands XCD x a contiguous range of (chunk, tile) ids, and a launch whose
-  // tile count does not divide the 32 CUs of an XCD (27 tiles for 256 -> 720) leaves one round badly filled:
-  // the candidates are priced with a greedy simulation of that mapping (per-workgroup cost = K steps + a
-  // fixed prologue / epilogue / partial-tile cost) and the cheapest wins.  Plans are cached per shape.
-  long long CH = 0;
-  // one round of the CUs the kernel may use: fewest split-K partials (opts.wgrad_target_blocks: no candidate search)
-  const bool g_big_target_user = p->opts.wgrad_target_blocks > 0;
-  const long long g_big_target_blocks = g_big_target_user ? p->opts.wgrad_target_blocks : rn_num_cus() - p->opts.reserved_cus;
-  {
-    static std::mutex mu;
-    static std::unordered_map<std::string, long long> cache;
-    std::string key((const char*)&g_big_target_blocks, sizeof(g_big_target_blocks));
-    key.push_back(g_big_target_user ? 1 : 0);
-    const int dims[4] = {a.R * 16 + a.S, a.Cin, a.Cout, p->num_segments};
-    key.append((const char*)dims, sizeof(dims));
-    for (int i = 0; i < p->num_segments; ++i) key.append((const char*)&a.seg[i].P, sizeof(a.seg[i].P));
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) {
-      CH = it->second;
-    } else {
-      const int mult_x2[4] = {2, 3, 4, 6};
-      const int ncand = g_big_target_user ? 1 : 4;
-      double best = 0;
-      for (int c = 0; c < ncand; ++c) {
-        const long long blocks = (long long)g_big_target_blocks * mult_x2[c] / 2;
-        long long target = blocks / tiles;
-        if (target < 1) target = 1;
-        long long ch = rn_cdiv(rn_cdiv(Ptot, target), BK) * BK;
-        if (ch < 4 * BK) ch = 4 * BK;
-        int chunks = 0;
-        for (int it2 = 0; it2 < 16; ++it2) {
-          chunks = 0;
-          for (int i = 0; i < p->num_segments; ++i) chunks += (int)rn_cdiv(a.seg[i].P, ch);
-          if ((long long)chunks * tiles <= blocks || chunks <= 1) break;
-          ch += BK * rn_cdiv(ch / BK, 16);    // +6 % per iteration
-        }
-        // greedy schedule of the kernel's XCD mapping: workgroup `logical` = chunk * tiles + tile
-        const long long total = (long long)chunks * tiles;
-        std::vector<int> steps;   // K steps of every chunk
-        for (int i = 0; i < p->num_segments; ++i)
-          for (long long b = 0; b < a.seg[i].P; b += ch)
-            steps.push_back((int)rn_cdiv(std::min<long long>(ch, a.seg[i].P - b), BK));
-        const double fixed = 30.0;   // prologue + epilogue + partial tile write, in K steps
-        double makespan = 0;
-        const long long q = total >> 3, rr = total & 7;
-        long long begin = 0;
-        for (int x = 0; x < 8; ++x) {
-          const long long n = q + (x < rr ? 1 : 0);
-          double cu[32];
-          for (int k = 0; k < 32; ++k) cu[k] = 0;
-          for (long long l = begin; l < begin + n; ++l) {
-            int k0 = 0;
-            for (int k = 1; k < 32; ++k) if (cu[k] < cu[k0]) k0 = k;
-            cu[k0] += steps[(size_t)(l / tiles)] + fixed;
-          }
-          for (int k = 0; k < 32; ++k) makespan = std::max(makespan, cu[k]);
-          begin += n;
-        }
-        if (c == 0 || makespan < best * 0.97) {   // more workgroups only for a clear gain
-          best = makespan;
-          CH = ch;
-        }
-      }
-      cache.emplace(key, CH);
-    }
-  }
-  a.CH = (int)CH;
-  int chunks = 0;
-  for (int i = 0; i < p->num_segments; ++i) {
-    WgSegDev& d = a.seg[i];
-    d.chunk_begin = chunks;
-    chunks += (int)rn_cdiv(d.P, CH);
-  }
-  a.total_chunks = chunks;
-  return true;
-}
-
-int rn_launch_wgrad_big(const WgArgs& a, const rn_launch_opts& opts, hipStream_t st) {
+int rn_launch_wgrad_big(const WgArgs& a, bool linear, unsigned grid, hipStream_t st) {
   static unsigned long long attr_set = 0;   // one bit per device
   if (RN_ATTRS_NEEDED(attr_set)) {
     RN_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_big_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -408,18 +309,8 @@ int rn_launch_wgrad_big(const WgArgs& a, const rn_launch_opts& opts, hipStream_t
                                      LDS_BYTES));
     RN_ATTRS_DONE(attr_set);
   }
-  bool linear = a.sh == 1 && a.sw == 1 && a.pt == (a.R - 1) / 2 && a.pl == (a.S - 1) / 2 && (a.R & 1) && (a.S & 1);
-  for (int i = 0; i < a.nseg; ++i) {
-    const WgSegDev& s = a.seg[i];
-    linear = linear && s.Ho == s.H && s.Wo == s.W &&
-             (long long)s.N * s.H * s.W * (s.xS > s.dyS ? s.xS : s.dyS) * 2 < (1ll << 31) - (1ll << 24);
-  }
-  int items = a.co_tiles * a.ci_tiles * a.R * a.S * a.total_chunks;
-  rn_launch_opts o = opts;
-  o.max_workgroups = 0;   // the cap is for the persistent convolution grids
-  dim3 grid((unsigned)(opts.reserved_cus > 0 ? rn_persistent_grid(items, rn_num_cus(), o) : items));
-  if (linear) hipLaunchKernelGGL(wgrad_big_kernel<true>, grid, dim3(512), LDS_BYTES, st, a);
-  else hipLaunchKernelGGL(wgrad_big_kernel<false>, grid, dim3(512), LDS_BYTES, st, a);
+  if (linear) hipLaunchKernelGGL(wgrad_big_kernel<true>, dim3(grid), dim3(512), LDS_BYTES, st, a);
+  else hipLaunchKernelGGL(wgrad_big_kernel<false>, dim3(grid), dim3(512), LDS_BYTES, st, a);
   RN_CHECK_LAUNCH();
   return RN_OK;
 }

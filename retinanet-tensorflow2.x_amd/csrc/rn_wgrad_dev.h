@@ -1,5 +1,6 @@
 // rn_wgrad_dev.h — declarations shared by the weight-gradient kernels (rn_wgrad.hip: 128 x 128 per-tap tiles;
-// rn_wgrad_big.hip: 256 x 256 per-tap tiles, ping-pong).
+// rn_wgrad_big.hip: 256 x 256 per-tap tiles, ping-pong; rn_wgrad_halo.hip: all nine taps of a 3x3 layer) and their
+// host-side planner (rn_wgrad_dispatch.hip).
 #ifndef RN_WGRAD_DEV_H_
 #define RN_WGRAD_DEV_H_
 #include "rn_common.h"
@@ -45,6 +46,9 @@ __device__ __forceinline__ bf16x8_t rn_tr_frag(rn_u32x2_t lo, rn_u32x2_t hi) {
 #define WG_BK 64
 #define WG_TILE_BYTES (WG_BK * 256)
 #define WG_OOB 0x80000000u
+#define WGB_BK 32         // K step (pixels) of wgrad_big_kernel
+#define WH_STRIP 16       // wgrad_halo_kernel: pixels across a column strip
+#define WH_STEP_ROWS 2    // wgrad_halo_kernel: padded image rows a step of a strip covers
 
 struct WgSegDev {
   const uint16_t* x;
@@ -83,12 +87,13 @@ struct WhArgs {
 struct WgDwPtrs {         // output tensors of the (grouped) split-K reduction
   float4* p[RN_WGRAD_MAX_GROUP];
 };
-bool rn_wgrad_halo_plan(const rn_wgrad_problem* const* ps, int ngroups, WhArgs& a);
-size_t rn_wgrad_halo_workspace_bytes(const WhArgs& a);
-int rn_launch_wgrad_halo(const WhArgs& a, const rn_launch_opts& opts, hipStream_t st);
 
-// rn_wgrad_big.hip: eligibility + plan (fills a.CH / chunk_begin / total_chunks / co_tiles / ci_tiles for
-// 256-wide tiles) and launch of the partial-tile kernel (same workspace layout as wgrad_kernel)
-bool rn_wgrad_big_plan(const rn_wgrad_problem* p, WgArgs& a);
-int rn_launch_wgrad_big(const WgArgs& a, const rn_launch_opts& opts, hipStream_t st);
+// The launch points of the kernel files: `a` as planned by rn_wgrad_dispatch.hip with ws set, the instantiation (LINEAR; the
+// halo kernel's probe-build variant = rn_launch_opts.ablate) and the grid.  Each sets its kernel attributes once per device.
+int rn_launch_wgrad128(const WgArgs& a, bool linear, unsigned grid, hipStream_t st);
+int rn_launch_wgrad_big(const WgArgs& a, bool linear, unsigned grid, hipStream_t st);
+int rn_launch_wgrad_halo(const WhArgs& a, int variant, unsigned grid, hipStream_t st);
+// rn_wgrad.hip: dws.p[g] = sum of layer g's `chunks` partial tiles [g][chunk][n4 float4] (+ beta * dws.p[g]), g < ngroups
+int rn_launch_wgrad_reduce(const void* workspace, long long n4, int chunks, const WgDwPtrs& dws, int blocks, int ngroups,
+                           float beta, hipStream_t st);
 #endif  // RN_WGRAD_DEV_H_

@@ -31,10 +31,6 @@
 // load-only step that brings its first two dy rows); a workgroup = (co tile, ci tile, chunk of consecutive steps) and
 // writes its 128 x 9 x 64 partial tile into the same workspace layout as the per-tap kernels
 // ([chunk][co][tap][ci]), summed in index order by wgrad_reduce_kernel: deterministic, no float atomics.
-#include <string.h>
-
-#include <algorithm>
-
 #include "rn_wgrad_dev.h"
 
 namespace {
@@ -353,76 +349,6 @@ __global__ void __launch_bounds__(512) wgrad_halo_kernel(const WhArgs args) {
 
 }  // namespace
 
-// Layers this kernel serves: 3x3 / stride 1 / pad 1, same-size output, Cin a multiple of 64, Cout a multiple of 8 and
-// at least 64.  Auto-selected when the launch holds at least 16 384 output pixels (rn_launch_opts.wgrad_kernel = 2:
-// whatever the pixel count; = 3: keep the per-tap wgrad_big_kernel for A/B timing).
-// ps[0..ngroups): layers of IDENTICAL geometry (rn_conv2d_nhwc_wgrad_group) — one launch, tiles = groups x co x ci, so
-// the split-K plan needs 1/ngroups of the pixel chunks per layer and writes 1/ngroups of the partial-tile bytes:
-// every workgroup of a launch writes its 288 KB accumulator once, 75 MB per launch however small the layer (measured:
-// eight head-tower layers as one launch 2.12 ms against 8 x 0.346 ms, tools/bench_wgrad.py presets tower8 / tower).
-bool rn_wgrad_halo_plan(const rn_wgrad_problem* const* ps, int ngroups, WhArgs& a) {
-  if (ngroups < 1 || ngroups > RN_WGRAD_MAX_GROUP) return false;
-  const rn_wgrad_problem* p = ps[0];
-  if (p->R != 3 || p->S != 3 || p->stride_h != 1 || p->stride_w != 1 || p->pad_top != 1 || p->pad_left != 1) return false;
-  if (p->opts.wgrad_kernel == 1 || p->opts.wgrad_kernel == 3) return false;
-  const int Cin = p->seg[0].Cin, Cout = p->seg[0].Cout;
-  if (Cin % 64 != 0 || Cout % 8 != 0 || Cout < 64) return false;
-  long long Ptot = 0, steps = 0;
-  a.nseg = p->num_segments;
-  a.ngroups = ngroups;
-  a.pad_ = 0;
-  for (int i = 0; i < p->num_segments; ++i) {
-    const rn_wgrad_segment& s = p->seg[i];
-    if (s.Ho != s.H || s.Wo != s.W || !s.x || !s.dy) return false;
-    WhSeg& d = a.seg[i];
-    d.N = s.N; d.H = s.H; d.W = s.W;
-    d.dyS = s.dy_pix_stride > 0 ? s.dy_pix_stride : s.Cout;
-    d.xS = s.x_pix_stride > 0 ? s.x_pix_stride : s.Cin;
-    d.ctiles = (int)rn_cdiv(s.W, 16);
-    // padded rows G = 1 .. N*(H+1) - 1 carry products; step t >= 1 of a strip covers G = 2t - 1, 2t; step 0 is load-only
-    d.L = (int)rn_cdiv((long long)s.N * (s.H + 1) - 1, 2) + 1;
-    d.step_begin = (int)steps;
-    d.pad_ = 0;
-    steps += (long long)d.ctiles * d.L;
-    Ptot += (long long)s.N * s.H * s.W;
-    if ((long long)s.N * s.H * s.W * (d.xS > d.dyS ? d.xS : d.dyS) * 2 >= (1ll << 31) - (1ll << 24)) return false;
-    for (int g = 0; g < ngroups; ++g) {      // the other layers: the same geometry, their own tensors
-      const rn_wgrad_problem* q = ps[g];
-      const rn_wgrad_segment& t = q->seg[i];
-      if (q->R != p->R || q->S != p->S || q->stride_h != p->stride_h || q->stride_w != p->stride_w ||
-          q->pad_top != p->pad_top || q->pad_left != p->pad_left || q->num_segments != p->num_segments ||
-          memcmp(&q->opts, &p->opts, sizeof(p->opts)) != 0 || t.N != s.N || t.H != s.H || t.W != s.W || t.Cin != s.Cin ||
-          t.Ho != s.Ho || t.Wo != s.Wo || t.Cout != s.Cout || t.dy_pix_stride != s.dy_pix_stride ||
-          t.x_pix_stride != s.x_pix_stride || !t.x || !t.dy)
-        return false;
-      a.ptr[g][i].x = (const uint16_t*)t.x;
-      a.ptr[g][i].dy = (const uint16_t*)t.dy;
-    }
-  }
-  if (Ptot < 16384 && p->opts.wgrad_kernel != 2) return false;
-  if (steps >= (1ll << 30)) return false;
-  a.Cin = Cin; a.Cout = Cout;
-  a.co_tiles = (int)rn_cdiv(Cout, 128);
-  a.ci_tiles = Cin / 64;
-  a.total_steps = (int)steps;
-  const int tiles = a.co_tiles * a.ci_tiles * ngroups;
-  // one round of the CUs the kernel may use: fewest split-K partials; a chunk is at least 24 steps long — every chunk
-  // writes a 288 KB partial tile — unless the caller asks for MORE workgroups than the chip has (the tests of the chunk
-  // seams do: short chunks on purpose).  The two-stream engine's CU cap (wgrad_target_blocks = 176) keeps 24.
-  long long blocks = p->opts.wgrad_target_blocks > 0 ? p->opts.wgrad_target_blocks : rn_num_cus() - p->opts.reserved_cus;
-  const long long min_steps = p->opts.wgrad_target_blocks > rn_num_cus() ? 2 : 24;
-  long long chunks = blocks / tiles;
-  if (chunks < 1) chunks = 1;
-  if (chunks > rn_cdiv(steps, min_steps)) chunks = rn_cdiv(steps, min_steps);
-  a.CHs = (int)rn_cdiv(steps, chunks);
-  a.total_chunks = (int)rn_cdiv(steps, a.CHs);
-  return true;
-}
-
-size_t rn_wgrad_halo_workspace_bytes(const WhArgs& a) {
-  return (size_t)a.ngroups * a.total_chunks * a.Cout * 9 * a.Cin * sizeof(float);
-}
-
 template <int VAR, int STAGES = WH_STAGES_DEFAULT>
 static int wh_launch(const WhArgs& a, dim3 grid, hipStream_t st) {
   static unsigned long long attr_set = 0;   // per template instantiation, one bit per device
@@ -436,13 +362,10 @@ static int wh_launch(const WhArgs& a, dim3 grid, hipStream_t st) {
   return RN_OK;
 }
 
-int rn_launch_wgrad_halo(const WhArgs& a, const rn_launch_opts& opts, hipStream_t st) {
-  const int items = a.ngroups * a.co_tiles * a.ci_tiles * a.total_chunks;
-  rn_launch_opts o = opts;
-  o.max_workgroups = 0;   // the cap is for the persistent convolution grids
-  dim3 grid((unsigned)(opts.reserved_cus > 0 ? rn_persistent_grid(items, rn_num_cus(), o) : items));
+int rn_launch_wgrad_halo(const WhArgs& a, int variant, unsigned grid_size, hipStream_t st) {
+  const dim3 grid(grid_size);
 #ifdef RN_PROBES
-  switch (opts.ablate) {
+  switch (variant) {
     case 1: return wh_launch<1>(a, grid, st);
     case 2: return wh_launch<2>(a, grid, st);
     case 4: return wh_launch<4>(a, grid, st);

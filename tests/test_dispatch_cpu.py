@@ -1,8 +1,9 @@
-"""Host logic of the convolution dispatcher (no GPU: rn_conv_kernel_id / rn_conv_tile_rows / rn_conv_bn_row_blocks /
-rn_conv_splitk_workspace_bytes are pure functions of the problem descriptor; without a device the library assumes the
-MI355X's 256 compute units).  Pins which kernel family, tile shape and split plan the layers of the bench configurations
-get — the policy DESIGN.md section 4 describes — so that a dispatcher edit shows up as a diff here, not as a silent
-slow-down on the GPU box."""
+"""Host logic of the convolution dispatchers (no GPU: rn_conv_kernel_id / rn_conv_tile_rows / rn_conv_bn_row_blocks /
+rn_conv_splitk_workspace_bytes and, for the weight gradients, rn_wgrad_kernel_id / rn_wgrad_workspace_bytes /
+rn_wgrad_group_fused / rn_wgrad_group_workspace_bytes are pure functions of the problem descriptors; without a device the
+library assumes the MI355X's 256 compute units).  Pins which kernel family, tile shape and split plan the layers of the
+bench configurations get — the policy DESIGN.md section 4 describes — so that a dispatcher edit shows up as a diff here,
+not as a silent slow-down on the GPU box."""
 import ctypes
 import json
 import os
@@ -133,6 +134,105 @@ def test_dispatch_table():
         if got != [kid, tile_rows, blocks, ws]:
             bad.append((B, k, stride, segs, f32, w_terms, w_pair, ws_bytes, opts, bias_res, got, [kid, tile_rows, blocks, ws]))
     assert not bad, (len(bad), bad[:5])
+
+# ---- weight gradients (rn_wgrad_dispatch.hip: wgrad_plan) -------------------------------------------------------------
+def _wgrad_layer(R, S, stride, pad, segs, opts):
+    p = _C.WgradProblem()
+    p.R, p.S, p.stride_h, p.stride_w, p.pad_top, p.pad_left = R, S, stride, stride, pad, pad
+    p.num_segments = len(segs)
+    for i, (N, H, W, Cin, Ho, Wo, Cout, dyS, xS, null) in enumerate(segs):
+        s = p.seg[i]
+        s.x, s.dy = (0 if null else 16), 16      # dummy addresses: the queries read them as "null or not" only
+        s.N, s.H, s.W, s.Cin, s.Ho, s.Wo, s.Cout, s.dy_pix_stride, s.x_pix_stride = N, H, W, Cin, Ho, Wo, Cout, dyS, xS
+    p.opts = _C.LaunchOpts(**opts)
+    return p
+
+
+def _wgrad_group(R, S, stride, pad, segs, opts, n, alt):
+    """n layers of one geometry; alt = [k, "segs" | "opts", value]: layer k has its own segments or options"""
+    layers = []
+    for i in range(n):
+        sg, op = segs, opts
+        if alt and alt[0] == i:
+            sg, op = (alt[2], opts) if alt[1] == "segs" else (segs, alt[2])
+        layers.append(_wgrad_layer(R, S, stride, pad, sg, op))
+    return layers
+
+
+def _wgrad_answers(layers):
+    lib = _C.lib()
+    n = len(layers)
+    arr = (ctypes.POINTER(_C.WgradProblem) * n)(*[ctypes.pointer(p) for p in layers])
+    return [[lib.rn_wgrad_kernel_id(ctypes.byref(p)) for p in layers],
+            [int(lib.rn_wgrad_workspace_bytes(ctypes.byref(p))) for p in layers],
+            lib.rn_wgrad_group_fused(arr, n), int(lib.rn_wgrad_group_workspace_bytes(arr, n))]
+
+
+def _dense(k, Cin, Cout, sizes, B=32):
+    return [[B, h, w, Cin, h, w, Cout, 0, 0, 0] for h, w in sizes]
+
+
+WGRAD_CASES = [
+    # name, (k, stride, pad), segments, layers in the group, then at batch 32 WITHOUT and WITH the engine's default cap
+    # (wgrad_target_blocks = 160 for the wide kernels, 208 for the 128-tile kernel): (kernel id of a layer, split-K chunks of
+    # a layer on its own, fused, chunks the group's workspace holds: the fused launch's or one layer's, whichever is more)
+    ("head towers: eight 3x3 256 layers over five levels, one launch", (3, 1, 1), _dense(3, 256, 256, PYR), 8, (2, 32, 1, 32), (2, 20, 1, 20)),
+    ("stage-3 3x3 256: five layers, one launch", (3, 1, 1), _dense(3, 256, 256, [(40, 40)]), 5, (2, 32, 1, 32), (2, 20, 1, 20)),
+    ("stage-2 3x3 128: three layers, one launch", (3, 1, 1), _dense(3, 128, 128, [(80, 80)]), 3, (2, 128, 1, 128), (2, 80, 1, 80)),
+    ("stage-4 3x3 512: two layers of 12 800 pixels (alone: 128 tiles; as a group: segments of one launch)", (3, 1, 1), _dense(3, 512, 512, [(20, 20)]), 2, (0, 4, 1, 8), (0, 2, 1, 6)),
+    ("stage-3 *_a 1x1 1024->256: five layers as segments", (1, 1, 0), _dense(1, 1024, 256, [(40, 40)]), 5, (1, 64, 1, 64), (1, 40, 1, 40)),
+    ("stage-3 *_out 1x1 256->1024: six layers as segments", (1, 1, 0), _dense(1, 256, 1024, [(40, 40)]), 6, (1, 64, 1, 64), (1, 40, 1, 40)),
+    ("stage-2 *_a 1x1 512->128: three layers as segments (128-tile kernel)", (1, 1, 0), _dense(1, 512, 128, [(80, 80)]), 3, (0, 128, 1, 129), (0, 52, 1, 54)),
+    ("class prediction 3x3 256->720 over five levels", (3, 1, 1), _dense(3, 256, 720, PYR), 1, (2, 10, 0, 10), (2, 6, 0, 6)),
+    ("box prediction 3x3 256->36 over five levels (Cout % 8: per-tap 128 tiles)", (3, 1, 1), _dense(3, 256, 36, PYR), 1, (0, 32, 0, 32), (0, 15, 0, 15)),
+    ("FPN output 3x3 256 at 80 x 80", (3, 1, 1), _dense(3, 256, 256, [(80, 80)]), 1, (2, 32, 0, 32), (2, 20, 0, 20)),
+    ("stem 7x7 stride 2 on the packed image (R = 7, S = 1, 32 channels, x_pix_stride 4)", (7, 2, 0), [[32, 646, 648, 32, 320, 320, 64, 0, 4, 0]], 1, (0, 74, 0, 74), (0, 30, 0, 30)),
+]
+
+
+@pytest.mark.parametrize("name,filt,segs,n,free,capped", WGRAD_CASES, ids=[c[0] for c in WGRAD_CASES])
+def test_wgrad_dispatch_of_the_bench_layers(name, filt, segs, n, free, capped):
+    k, stride, pad = filt
+    R, S = (k, 1) if name.startswith("stem") else (k, k)
+    weight_bytes = segs[0][6] * R * S * segs[0][3] * 4
+    for want, cap in ((free, False), (capped, True)):
+        opts = {"wgrad_target_blocks": 208 if want[0] == 0 else 160} if cap else {}
+        kids, wss, fused, gws = _wgrad_answers(_wgrad_group(R, S, stride, pad, segs, opts, n, None))
+        assert kids == [want[0]] * n, (cap, kids)
+        assert [w / weight_bytes for w in wss] == [want[1]] * n, (cap, wss)      # workspace = chunks x |W| x 4 bytes
+        assert fused == want[2], (cap, fused)
+        assert gws / weight_bytes == want[3], (cap, gws)
+
+
+def test_wgrad_dispatch_table():
+    """The weight-gradient policy: tests/golden/wgrad_dispatch_table.json holds (filter, segments, rn_launch_opts, layers in
+    the group and the one layer that differs) -> (rn_wgrad_kernel_id and rn_wgrad_workspace_bytes per layer,
+    rn_wgrad_group_fused, rn_wgrad_group_workspace_bytes) as the library answered BEFORE the decisions moved into one plan
+    (rn_wgrad_dispatch.hip: wgrad_plan) — recorded from that library, 256 compute units, never from the planner.  Workspace
+    bytes / weight bytes is the number of split-K chunks, so the rows pin the split plan and not only the kernel family.
+    The rows are one descriptor of every distinct outcome (kernel ids x fused or not x which need sets the group's workspace
+    x rejected or not x kind of odd layer) with each value of every axis of a grid of 1 052 968 descriptors (688 326 of them
+    groups of 2 / 5 / 8 / 9 layers): batch 1 / 2 / 8 / 32, the pyramid sizes, 37 x 37 and 24 x 56 (pixel totals on both sides
+    of 16 384), 1x1, 3x3 stride 1 / 2, the stem form (7 x 1, 32 channels, x_pix_stride 4), a strided dy, 19 channel pairs
+    (2048 -> 2048 3x3: 576 tiles of 256, which wgrad_big_kernel refuses), 1 / 3 / 5 segments, wgrad_kernel 0 - 3,
+    wgrad_target_blocks 0 / 1 / 64 / 160 / 176 / 208 / 300, reserved_cus 0 / 8; groups of identical layers that the halo kernel
+    serves and that it does not (layers as segments), with one layer of another shape, with one layer of other options; and
+    every rejection (Cin % 8, Cout % 4, a null tensor, 2^24 pixels, 2 GiB tensors, no segments, bad strides, bad options) alone
+    and inside a group.  (A merged plan whose chunk count does not divide by the group size cannot be built: layers of
+    identical geometry get equal chunk counts.)  The library must reproduce every row."""
+    with open(os.path.join(os.path.dirname(__file__), "golden", "wgrad_dispatch_table.json")) as f:
+        rows = json.load(f)["rows"]
+    assert 300 <= len(rows) <= 2500
+    assert {k for r in rows for k in r[8]} == {-1, 0, 1, 2}          # every kernel, and the rejections
+    assert {r[10] for r in rows} == {0, 1}                           # both answers of rn_wgrad_group_fused
+    assert any(r[11] == 0 for r in rows) and any(r[9] == [0] for r in rows)
+    bad = []
+    for R, S, stride, pad, segs, opts, n, alt, kids, wss, fused, gws in rows:
+        got = _wgrad_answers(_wgrad_group(R, S, stride, pad, segs, opts, n, alt))
+        if got != [kids, wss, fused, gws]:
+            bad.append((R, S, stride, pad, segs, opts, n, alt, got, [kids, wss, fused, gws]))
+    assert not bad, (len(bad), bad[:5])
+
 
 def _bn_problem(segs):
     p = _C.BnProblem()
