@@ -449,7 +449,9 @@ int rn_scatter_add2x(const void* x, void* y, int N, int H, int W, int C, int Ho,
 /* y[n, 2i+a, 2j+b, c] (+)= x[n, i, j, (a*2+b)*C + c]; x bf16 [N,H,W,4C], y bf16 [N,2H,2W,C] */
 int rn_depth_to_space2x(const void* x, void* y, int N, int H, int W, int C, int accumulate, void* stream);
 int rn_cast_f32_to_bf16(const float* x, void* y, int64_t n, void* stream);
-/* dy = dz * act'(z) for a layer with an activation but no BatchNorm in front */
+/* dy = dz * act'(z) for a layer with an activation but no BatchNorm in front: act = none | relu | relu6, whose
+ * derivative is a function of the stored output z.  act = swish is refused with RN_EINVAL before anything is launched
+ * (dy is not written): swish' needs the pre-activation, which is not among the arguments. */
 int rn_act_bwd(const void* dz, const void* z, void* dy, int64_t n, int act, void* stream);
 
 /* ---------------------------------------------------------------------------------------
@@ -462,8 +464,15 @@ int rn_act_bwd(const void* dz, const void* z, void* dy, int64_t n, int act, void
  *   rn_bn_apply        z = act((y*scale + shift) [* sample_scale[n]] + residual); the BatchNorm output, the
  *                      drop_connect output and (in front of swish) the residual sum are rounded to bf16 where the
  *                      reference holds a bf16 tensor between two layers (see rn_conv_segment)
- *   rn_bn_bwd_reduce   dz, z, y -> bsums[2][C] = (sum g, sum g*xhat), g = dz*act'(z); also dbeta = bsums[0],
- *                      dgamma = bsums[1]: the gamma / beta gradients are THIS replica's sums
+ *   rn_bn_bwd_reduce   dz, z, y -> bsums[2][C] = (sum g, sum g*xhat), g = dz*act'(.); also dbeta = bsums[0],
+ *                      dgamma = bsums[1]: the gamma / beta gradients are THIS replica's sums.
+ *                      The gate act'(.): relu / relu6 — 1 where the stored z is > 0 (and < 6), from z, from the bit mask
+ *                      (rn_bn_segment.act_mask) or, without a residual input, from u = y*scale + shift, which decides
+ *                      the same; swish — s + v*s*(1 - s), s = sigmoid(v), at the value rn_bn_apply fed to swish when the
+ *                      segment has a residual input, v = rb(rb(y*scale + shift) + residual) (the residual tensor is read
+ *                      again), and at the fp32 v = y*scale + shift when it has none.  Segments of one problem may
+ *                      disagree on having a residual input (a slower, generic form of the passes; it needs z behind a
+ *                      relu / relu6 residual add).  swish with sample_scale is refused.
  *   (SyncBN: all-reduce `bsums` — after rn_bn_bwd_reduce, so dgamma / dbeta stay local like tf.gradients leaves them
  *    until the optimizer's cross-replica sum)
  *   rn_bn_bwd_apply    dy = scale*(g - sum_g/n - xhat*sum_gxhat/n); dres (+)= g
@@ -552,7 +561,10 @@ int rn_bn_bwd_colsum_chunks(const rn_bn_problem* problem, int segment);
 /* backward of K6/K7/K8 */
 int rn_maxpool2d_nhwc_bwd(const void* x, const void* dy, void* dx, int N, int H, int W, int C, int k, int stride,
                           int pad_top, int pad_left, int Ho, int Wo, int accumulate, void* stream);
-/* one level of the FPN top-down backward: din = (dout + sum2x2(din_finer)) * act'(out) */
+/* one level of the FPN top-down backward: din = (dout + sum2x2(din_finer)) * act'(out); din_finer NULL on the finest
+ * level, out NULL (or act = none) for no gate.  act = none | relu | relu6; act = swish with out != NULL is refused with
+ * RN_EINVAL before anything is launched (din is not written): swish' needs the sum in front of the activation, which is
+ * not among the arguments. */
 int rn_fpn_topdown_bwd_level(const void* dout, const void* din_finer, const void* out, void* din, int N, int H,
                              int W, int C, int act, void* stream);
 /* davg_scratch: rn_balance_features_bwd_scratch_bytes() bytes — d_avg at the intermediate level, then one byte per (pixel,

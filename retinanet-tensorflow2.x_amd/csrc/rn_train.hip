@@ -50,7 +50,9 @@ __device__ __forceinline__ float act_mask_u(float u, int act) {
   return 1.0f;
 }
 // d act(u) / du: relu / relu6 from the stored output z, swish from the recomputed pre-activation u
-// (swish'(u) = s + u*s*(1-s), s = sigmoid(u); tf.nn.swish's registered gradient)
+// (swish'(u) = s + u*s*(1-s), s = sigmoid(u); tf.nn.swish's registered gradient).  u is what bn_apply_kernel fed to
+// swish when the segment has a residual input — rb(rb(y*scale + shift) + residual), see bn_swish_input() — and the
+// fp32 y*scale + shift when it has none.
 __device__ __forceinline__ float act_deriv(float z, float u, int act) {
   if (act == RN_ACT_SWISH) {
     const float sg = 1.0f / (1.0f + __expf(-u));
@@ -64,7 +66,12 @@ __device__ __forceinline__ float act_deriv(float z, float u, int act) {
 // compares and branches PER ELEMENT — the passes are then issue-bound, not HBM-bound).
 // G_MASK: relu / relu6 behind a residual add with the gate stored by the forward pass as ONE BIT per element
 // (rn_bn_segment.act_mask): the backward passes read P*C/8 bytes instead of the 2*P*C of z.
-enum { G_GENERIC = 0, G_NONE = 1, G_U_RELU = 2, G_U_RELU6 = 3, G_Z_RELU = 4, G_Z_RELU6 = 5, G_SWISH = 6, G_MASK = 7 };
+// G_SWISH_RES: swish behind a residual add — the gate is taken at the sum the forward pass fed to swish, so the passes
+// read the residual tensor too (G_SWISH, every segment without a residual: EfficientNet's expand / depthwise layers).
+enum { G_GENERIC = 0, G_NONE = 1, G_U_RELU = 2, G_U_RELU6 = 3, G_Z_RELU = 4, G_Z_RELU6 = 5, G_SWISH = 6, G_MASK = 7,
+       G_SWISH_RES = 8 };
+// the input of swish in a segment with a residual: bn_apply_kernel's two roundings (BatchNorm output, Add output)
+__device__ __forceinline__ float bn_swish_input(float u, float res) { return rn_rb(rn_rb(u) + res); }
 template <int G>
 __device__ __forceinline__ float grad_gate(float dz, float z, float u, int act, bool from_u) {
   if (G == G_NONE || G == G_MASK) return dz;                     // G_MASK: the caller applies the stored bit
@@ -75,7 +82,7 @@ __device__ __forceinline__ float grad_gate(float dz, float z, float u, int act, 
   }
   if (G == G_Z_RELU) return z > 0.0f ? dz : 0.0f;
   if (G == G_Z_RELU6) return (z > 0.0f && z < 6.0f) ? dz : 0.0f;
-  if (G == G_SWISH) {
+  if (G == G_SWISH || G == G_SWISH_RES) {   // (G_SWISH_RES: the caller passes u = bn_swish_input())
     // v_rcp_f32 (1 ulp) instead of the correctly rounded division the build flags give `/` (~10 instructions): the
     // swish passes of EfficientNet are VALU-bound, and the gate is a factor of a gradient that is rounded to 16 bits
     const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-u));
@@ -86,10 +93,10 @@ __device__ __forceinline__ float grad_gate(float dz, float z, float u, int act, 
 // the gate mode of a problem: one mode when every segment agrees on "has a residual input", else generic
 static int bn_gate_mode(const rn_bn_problem* p) {
   if (p->act == RN_ACT_NONE) return G_NONE;
-  if (p->act == RN_ACT_SWISH) return G_SWISH;
   int with_res = 0;
   for (int i = 0; i < p->num_segments; ++i) with_res += p->seg[i].residual ? 1 : 0;
   if (with_res != 0 && with_res != p->num_segments) return G_GENERIC;
+  if (p->act == RN_ACT_SWISH) return with_res ? G_SWISH_RES : G_SWISH;
   if (with_res == 0) return p->act == RN_ACT_RELU ? G_U_RELU : (p->act == RN_ACT_RELU6 ? G_U_RELU6 : G_GENERIC);
   int with_mask = 0;
   for (int i = 0; i < p->num_segments; ++i) with_mask += p->seg[i].act_mask ? 1 : 0;
@@ -105,6 +112,7 @@ static int bn_gate_mode(const rn_bn_problem* p) {
     case G_Z_RELU6: CALL_(G_Z_RELU6); break;            \
     case G_SWISH: CALL_(G_SWISH); break;                \
     case G_MASK: CALL_(G_MASK); break;                  \
+    case G_SWISH_RES: CALL_(G_SWISH_RES); break;        \
     default: CALL_(G_GENERIC); break;                   \
   }
 
@@ -191,14 +199,18 @@ __global__ void __launch_bounds__(TR_THREADS) bn_colreduce_kernel(const BnArgs a
         const bool from_u = !s.residual && (a.act == RN_ACT_RELU || a.act == RN_ACT_RELU6);
         constexpr bool need_z = G == G_Z_RELU || G == G_Z_RELU6 || G == G_GENERIC;
         bf8 z;
-        if (need_z && (G != G_GENERIC || (a.act != RN_ACT_NONE && !from_u))) z = unpack8(s.z[o]);
+        if (need_z && (G != G_GENERIC || (a.act != RN_ACT_NONE && a.act != RN_ACT_SWISH && !from_u))) z = unpack8(s.z[o]);
         unsigned bits = 0xffu;
         if (G == G_MASK) bits = s.mask[o];
+        const bool swish_res = G == G_SWISH_RES || (G == G_GENERIC && a.act == RN_ACT_SWISH && s.residual != nullptr);
+        bf8 res;
+        if (swish_res) res = unpack8(s.residual[o]);
         float m = 1.0f;
         if (s.sample_scale) m = s.sample_scale[(int)r / (int)s.rows_per_sample];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          const float u = y.v[q] * scq[q] + shq[q];
+          float u = y.v[q] * scq[q] + shq[q];
+          if (swish_res) u = bn_swish_input(u, res.v[q]);
           float g = grad_gate<G < 0 ? 0 : G>(dz.v[q], z.v[q], u, a.act, from_u) * m;
           if (G == G_MASK) g = ((bits >> q) & 1u) ? g : 0.0f;
           s0[q] += g;
@@ -573,14 +585,18 @@ __global__ void __launch_bounds__(TR_THREADS) bn_bwd_apply_kernel(const BnArgs a
     const bool from_u = !s.residual && (a.act == RN_ACT_RELU || a.act == RN_ACT_RELU6);
     constexpr bool need_z = G == G_Z_RELU || G == G_Z_RELU6 || G == G_GENERIC;
     bf8 z;
-    if (need_z && (G != G_GENERIC || (a.act != RN_ACT_NONE && !from_u))) z = unpack8(s.z[i]);
+    if (need_z && (G != G_GENERIC || (a.act != RN_ACT_NONE && a.act != RN_ACT_SWISH && !from_u))) z = unpack8(s.z[i]);
     const float m = s.sample_scale ? s.sample_scale[(int)(i / C8) / (int)s.rows_per_sample] : 1.0f;
     unsigned bits = 0xffu;
     if (G == G_MASK) bits = s.mask[i];
+    const bool swish_res = G == G_SWISH_RES || (G == G_GENERIC && a.act == RN_ACT_SWISH && s.residual != nullptr);
+    bf8 res;
+    if (swish_res) res = unpack8(s.residual[i]);
     bf8 g, o;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      const float u = y.v[q] * sc[q] + shq[q];
+      float u = y.v[q] * sc[q] + shq[q];
+      if (swish_res) u = bn_swish_input(u, res.v[q]);
       g.v[q] = grad_gate<G>(dz.v[q], z.v[q], u, a.act, from_u);
       if (G == G_MASK) g.v[q] = ((bits >> q) & 1u) ? g.v[q] : 0.0f;
       const float xh = (y.v[q] - mean[q]) * istd[q];
@@ -756,6 +772,9 @@ static int bn_colreduce(const rn_bn_problem* p, int mode, void* ws, size_t ws_by
     const BnSegDev& s = a.seg[i];
     RN_CHECK_ARG(s.y && (mode == 0 ? s.sums != nullptr : (s.dz && s.bsums && s.fwd)), "%s: null tensor", fn);
     RN_CHECK_ARG(mode == 0 || a.act == RN_ACT_NONE || s.z || s.mask, "%s: z needed for the activation mask", fn);
+    // (the generic gate of a mixed problem reads z, never the bit mask, behind a residual add)
+    RN_CHECK_ARG(mode == 0 || bn_gate_mode(p) != G_GENERIC || a.act == RN_ACT_SWISH || !s.residual || s.z,
+                 "%s: z needed for the activation mask", fn);
     if (s.chunks > max_chunks) max_chunks = s.chunks;
     if (s.nslab > max_slabs) max_slabs = s.nslab;
     if (s.C > max_c) max_c = s.C;
@@ -864,6 +883,8 @@ extern "C" int rn_bn_bwd_apply(const rn_bn_problem* p, void* stream) {
     RN_CHECK_ARG(a.seg[i].y && a.seg[i].dz && a.seg[i].dy && a.seg[i].fwd && a.seg[i].bsums,
                  "rn_bn_bwd_apply: null tensor");
     RN_CHECK_ARG(a.act == RN_ACT_NONE || a.seg[i].z || a.seg[i].mask, "rn_bn_bwd_apply: z needed for the activation mask");
+    RN_CHECK_ARG(bn_gate_mode(p) != G_GENERIC || a.act == RN_ACT_SWISH || !a.seg[i].residual || a.seg[i].z,
+                 "rn_bn_bwd_apply: z needed for the activation mask");
     const long long t = a.seg[i].P * (a.seg[i].C / 8);
     if (t > mx) mx = t;
   }
@@ -881,6 +902,7 @@ extern "C" int rn_bn_bwd_apply(const rn_bn_problem* p, void* stream) {
 }
 
 // ---- gradient of an activation without BN (prediction-free layers): dy = dz * mask(z) --------
+// none / relu / relu6 only: the host entry refuses swish, whose derivative is no function of z
 __global__ void __launch_bounds__(TR_THREADS)
 act_bwd_kernel(const uint4* __restrict__ dz, const uint4* __restrict__ z, uint4* __restrict__ dy, long long n8,
                int act) {
@@ -1043,6 +1065,7 @@ extern "C" int rn_depth_to_space2x(const void* x, void* y, int N, int H, int W, 
 
 extern "C" int rn_act_bwd(const void* dz, const void* z, void* dy, int64_t n, int act, void* stream) {
   RN_CHECK_ARG(dz && z && dy && n > 0 && n % 8 == 0, "rn_act_bwd: bad argument");
+  RN_CHECK_ARG(act != RN_ACT_SWISH, "rn_act_bwd: swish' needs the pre-activation, which is not an argument (only z is)");
   hipLaunchKernelGGL(act_bwd_kernel, dim3(tr_blocks(n / 8)), dim3(TR_THREADS), 0, (hipStream_t)stream,
                      (const uint4*)dz, (const uint4*)z, (uint4*)dy, (long long)(n / 8), act);
   RN_CHECK_LAUNCH();
@@ -1141,6 +1164,8 @@ topdown_bwd_kernel(const uint4* __restrict__ dout, const uint4* __restrict__ din
 extern "C" int rn_fpn_topdown_bwd_level(const void* dout, const void* din_finer, const void* out, void* din, int N,
                                         int H, int W, int C, int act, void* stream) {
   RN_CHECK_ARG(dout && din && C % 8 == 0 && N > 0 && H > 0 && W > 0, "rn_fpn_topdown_bwd_level: bad argument");
+  RN_CHECK_ARG(!(out && act == RN_ACT_SWISH),
+               "rn_fpn_topdown_bwd_level: swish' needs the pre-activation sum, which is not an argument (only out is)");
   hipLaunchKernelGGL(topdown_bwd_kernel, dim3(tr_blocks((long long)N * H * W * (C / 8))), dim3(TR_THREADS), 0,
                      (hipStream_t)stream, (const uint4*)dout, (const uint4*)din_finer, (const uint4*)out,
                      (uint4*)din, N, H, W, C / 8, act);

@@ -1065,6 +1065,11 @@ class TrainEngine:
             elif kind == "topdown":
                 op = item
                 L = len(op["ins"])
+                if op["act"] == "swish":
+                    # rn_fpn_topdown_bwd_level refuses it: swish' needs the sum in front of the activation, and the
+                    # forward pass keeps only its output
+                    raise NotImplementedError(f"backward of the top-down op {op['outs'][0]} .. {op['outs'][-1]} with "
+                                              "activation 'swish' is not built (relu / relu6 / none are)")
                 act = _C.ACT_IDS[op["act"]]
                 prev = None
                 for l in range(L):
@@ -1269,6 +1274,9 @@ class TrainEngine:
                     dyb = torch.zeros(shp, dtype=self.h16, device=self.dev)
                     dy_of[op["out"]] = dyb
                 else:
+                    if op["act"] == "swish":     # rn_act_bwd refuses it: swish' is no function of the stored output
+                        raise NotImplementedError(f"backward of the conv op {op['out']} ({op['conv']}): activation "
+                                                  "'swish' without a BatchNorm in front is not built")
                     dyb = torch.empty_like(self.t[op["out"]])
                     dy_of[op["out"]] = dyb
                     a = (self.grad[op["out"]].data_ptr(), self.t[op["out"]].data_ptr(), dyb.data_ptr(),
