@@ -38,6 +38,8 @@ typedef enum {
 
 enum { RN_DT_F32 = 0, RN_DT_BF16 = 1 };
 enum { RN_ACT_NONE = 0, RN_ACT_RELU = 1, RN_ACT_RELU6 = 2, RN_ACT_SWISH = 3 };
+/* FeatureFusion modes of the weighted FPN top-down entry points (K7); 'sum' is rn_fpn_topdown */
+enum { RN_FUSION_FAST_ATTENTION = 1, RN_FUSION_FAST_CHANNEL_ATTENTION = 2 };
 
 const char* rn_last_error(void);
 /* library ABI version; bumped when a signature changes */
@@ -567,6 +569,27 @@ int rn_maxpool2d_nhwc_bwd(const void* x, const void* dy, void* dx, int N, int H,
  * not among the arguments. */
 int rn_fpn_topdown_bwd_level(const void* dout, const void* din_finer, const void* out, void* din, int N, int H,
                              int W, int C, int act, void* stream);
+/* One level j of the backward of rn_fpn_topdown_fused (derivative of the unrounded function, fp32, one rounding per stored
+ * tensor), [N,H,W,C] the level's shape:
+ *   t = dout + (g_finer ? c_u(coef_finer) * sum2x2(g_finer) : 0);   g = rs(t * act'(out));   din = rs(c_l(coef) * g)
+ *   partials of Sl[c] = sum_{n,y,x} g * in_lower and Su[c] = sum_{n,y,x} g * up2(out_upper) over the STORED g, one f32
+ *   [2][C] row per workgroup in `workspace` (rn_fpn_fused_bwd_workspace_bytes(N,H,W,C) bytes — the rows, then room for the
+ *   finalised per-channel sums; RN_ENOMEM when smaller):
+ *   stage 1 of a deterministic two-stage reduction, the same bits on every run and stream.
+ * out_upper is out[j+1] [N,H/2,W/2,C]; g may alias dout.  The top level (no fusion below its output: in_lower, out_upper,
+ * coef, g and workspace NULL) has no gate and no sums: din = rs(dout + c_u(coef_finer) * sum2x2(g_finer)).
+ * act = none | relu | relu6 gate on `out` (out NULL: no gate); act = swish with out != NULL is refused with RN_EINVAL
+ * before anything is launched, like rn_fpn_topdown_bwd_level.
+ * rn_fpn_fused_bwd_finalize: stage 2.  sums (optional) f32 [2][C] = Sl, Su; with a_l, a_u, s of `coef`
+ *   da_l = (Sl (s - a_l) - Su a_u) / s^2,  da_u = (Su (s - a_u) - Sl a_l) / s^2,  dw = da * [w > 0]
+ * overwritten into dw_lower / dw_upper (C elements, or 1 for fast_attention: Sl, Su summed over the channels first). */
+size_t rn_fpn_fused_bwd_workspace_bytes(int N, int H, int W, int C);
+int rn_fpn_fused_bwd_level(const void* dout, const void* g_finer, const void* coef_finer, const void* out,
+                           const void* in_lower, const void* out_upper, const void* coef, void* g, void* din,
+                           void* workspace, size_t workspace_bytes, int N, int H, int W, int C, int act, void* stream);
+int rn_fpn_fused_bwd_finalize(void* workspace, size_t workspace_bytes, int N, int H, int W, int C,
+                              const float* w_lower, const float* w_upper, const void* coef, int mode, float* sums,
+                              float* dw_lower, float* dw_upper, void* stream);
 /* davg_scratch: rn_balance_features_bwd_scratch_bytes() bytes — d_avg at the intermediate level, then one byte per (pixel,
  * channel) of every coarser level: where in its pooling window the average has its first maximum, found once per coarse
  * pixel instead of by every fine pixel of the window.  RN_ENOMEM when too small. */
@@ -691,12 +714,29 @@ int rn_bottleneck64_pack(const float* wa_hwio, const float* wb_hwio, const float
                          void* packed, void* stream);
 int rn_bottleneck64_fwd(const rn_bottleneck64_problem* problem, void* stream);
 
-/* K7 (a6)  FPN top-down path, FeatureFusion mode 'sum' + NearestUpsampling2D + activation
- * (fpn.py:93-98, feature_fusion.py:41-56, nearest_upsampling.py:19-21):
+/* K7 (a6)  FPN top-down path, FeatureFusion + NearestUpsampling2D + activation
+ * (fpn.py:93-98, feature_fusion.py:41-56, nearest_upsampling.py:19-21).  Mode 'sum':
  * for l = num_levels-1 .. 1: out[l-1] = act(in[l-1] + up2(out[l])), out[top] = in[top] (not
  * written); p[l] bf16 [N,H0>>l,W0>>l,C] with level 0 the finest; out must not alias in. */
 int rn_fpn_topdown(void* const* p_in /* host array of device ptrs */, void* const* p_out, int num_levels,
                    int N, int H0, int W0, int C, int act, void* stream);
+/* Modes 'fast_attention' / 'fast_channel_attention' (feature_fusion.py:44-54): fusion j (levels j and j+1, j = 0 ..
+ * num_levels-2) owns two f32 variables w_lower[j], w_upper[j] of 1 (fast_attention) or C (fast_channel_attention)
+ * elements in DEVICE memory.  With rs() = one rounding to the 16-bit storage type, one rounding per TF op:
+ *   a_l = rs(max(w_l, 0)), a_u = rs(max(w_u, 0)), s = rs(rs(a_l + a_u) + rs(1e-4))
+ *   out[j] = rs(act(rs( rs(rs(in[j] * a_l) / s) + rs(rs(up2(out[j+1]) * a_u) / s) ))),   out[top] = in[top] (not written)
+ * rn_fpn_topdown_fused first launches a preparation kernel that reads the weights and writes coef[j]
+ * (rn_fpn_fusion_coef_bytes(C) bytes each, 16-byte aligned: a_l, a_u, s as storage values [3][C], then c_l = a_l / s and
+ * c_u = a_u / s as f32 [2][C]; a fast_attention scalar is repeated per channel), then rn_fpn_topdown_fused_launches()
+ * top-down launches cut like rn_fpn_topdown's.  The weights are read on the device when the launch runs: a captured
+ * launch replays with the values the buffers hold then.  The backward entry points read the coef blocks the forward
+ * pass of the same step wrote. */
+size_t rn_fpn_fusion_coef_bytes(int C);
+int rn_fpn_topdown_fused_launches(int num_levels, int N, int H0, int W0, int C);   /* host only; 0: bad pyramid */
+int rn_fpn_topdown_fused(void* const* p_in /* host array of device ptrs */, void* const* p_out,
+                         const float* const* w_lower /* host array [num_levels-1] of device ptrs */,
+                         const float* const* w_upper, void* const* coef, int num_levels, int N, int H0, int W0, int C,
+                         int act, int mode, void* stream);
 
 /* K8 (a7)  BalanceFeatures  (balance_features.py:19-60); out[l] may alias in[l];
  * mid = index of the intermediate level; scratch: bf16 [N,Hmid,Wmid,C]. */

@@ -19,8 +19,10 @@ LIB_PATH_F16 = os.environ.get("RNET_HIP_LIB_F16") or os.path.join(_HERE, "librne
 RN_DT_F32, RN_DT_BF16 = 0, 1
 RN_OK, RN_EINVAL, RN_ENOMEM, RN_EHIP, RN_ECOMM, RN_EUNSUPPORTED = 0, -1, -2, -3, -4, -5   # rn_status
 RN_ACT_NONE, RN_ACT_RELU, RN_ACT_RELU6, RN_ACT_SWISH = 0, 1, 2, 3
+RN_FUSION_FAST_ATTENTION, RN_FUSION_FAST_CHANNEL_ATTENTION = 1, 2
+FUSION_IDS = {"fast_attention": RN_FUSION_FAST_ATTENTION, "fast_channel_attention": RN_FUSION_FAST_CHANNEL_ATTENTION}
 RN_CONV_MAX_SEGMENTS = 10
-ABI_VERSION = 8
+ABI_VERSION = 9
 # f32 kernels of the dtype=float32 prediction convs (detection_head.py:80-88) as split-bf16 planes (rn_conv_segment.w_terms)
 PRED_W_TERMS = int(os.environ.get("RNET_PRED_W_TERMS", "2"))
 ACT_IDS = {None: RN_ACT_NONE, "none": RN_ACT_NONE, "relu": RN_ACT_RELU, "relu6": RN_ACT_RELU6,
@@ -218,6 +220,10 @@ _SIGNATURES = {
                                       c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rn_fpn_topdown_bwd_level": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                          c_int, c_void_p]),
+    "rn_fpn_fused_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "rn_fpn_fused_bwd_level": (c_int, [c_void_p] * 10 + [c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "rn_fpn_fused_bwd_finalize": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rn_balance_features_bwd_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "rn_balance_features_bwd": (c_int, [_PP, _PP, _PP, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int,
                                         c_int, c_void_p]),
@@ -242,6 +248,9 @@ _SIGNATURES = {
     "rn_maxpool2d_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_void_p]),
     "rn_fpn_topdown": (c_int, [_PP, _PP, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "rn_fpn_fusion_coef_bytes": (c_size_t, [c_int]),
+    "rn_fpn_topdown_fused_launches": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "rn_fpn_topdown_fused": (c_int, [_PP, _PP, _PP, _PP, _PP, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rn_balance_features": (c_int, [_PP, _PP, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "rn_create": (c_int, [c_int, POINTER(c_void_p)]),
     "rn_destroy": (c_int, [c_void_p]),
@@ -373,6 +382,14 @@ def ptr_array(tensors):
     arr = (c_void_p * len(tensors))()
     for i, t in enumerate(tensors):
         arr[i] = None if t is None else t.data_ptr()
+    return ctypes.cast(arr, _PP)
+
+
+def ptr_array_of(addresses):
+    """`ptr_array` for plain integer addresses"""
+    arr = (c_void_p * len(addresses))()
+    for i, a in enumerate(addresses):
+        arr[i] = a
     return ctypes.cast(arr, _PP)
 
 

@@ -17,7 +17,7 @@ import torch
 
 from retinanet import _C
 from .bottleneck import Bottleneck64, fused_blocks
-from .forward import (FoldedConvs, conv_launch_name, conv_problem, dw_problem, fold_bn, maxpool_step, split_by_depth, stem_input,
+from .forward import (FoldedConvs, FusionState, conv_launch_name, conv_problem, dw_problem, fold_bn, maxpool_step, split_by_depth, stem_input,
                       stem_pool_partner, stem_pool_step, stem_problem, tensor_readers, topdown_step)
 from .forward import pixel_pair_kernel, pixel_pair_ok  # noqa: F401  (host-side helpers, importable from here as before)
 
@@ -111,6 +111,10 @@ class InferenceEngine:
                 fc.refold(op["out"], fold_bn(variables, op.get("bn"), None, self.eps, self.dev))
             elif op["op"] in ("conv", "stem") and op["out"] not in self._bneck_skip:   # fused blocks: packed below
                 fc.load(variables, op)
+            elif op["op"] == "topdown" and op.get("fusion"):
+                # f32, copied in place: the top-down launch (captured or not) reads them on the device
+                for name in (n for pair in op["fusion_vars"] for n in pair):
+                    fc.stable(name, variables[name].to(self.dev, torch.float32).reshape(-1).clone())
         for fb in self.bneck.values():
             fb.load(variables, self.eps)
 
@@ -252,7 +256,11 @@ class InferenceEngine:
                 self.steps.append((maxpool_step(lib, op, self.t, B), "maxpool:" + op["out"]))
                 self.step_io["maxpool:" + op["out"]] = ({op["inp"]}, {op["out"]})
             elif kind == "topdown":
-                self.steps.append((topdown_step(lib, op, self.t, B, self._keep), "fpn_topdown"))
+                fusion = None
+                if op.get("fusion"):
+                    fusion = FusionState(lib, op, self.t[op["ins"][0]].shape[3], self.dev,
+                                         lambda n: self.folded.packed[n].data_ptr())
+                self.steps.append((topdown_step(lib, op, self.t, B, self._keep, fusion), "fpn_topdown"))
                 self.step_io["fpn_topdown"] = (set(op["ins"]), set(op["outs"]))
             elif kind == "balance":
                 ts = [self.t[n] for n in op["tensors"]]

@@ -333,10 +333,31 @@ def maxpool_step(lib, op, t, B):
     return lambda st: _C.check(lib.rn_maxpool2d_nhwc(*a, st), "rn_maxpool2d_nhwc")
 
 
-def topdown_step(lib, op, t, B, keep):
-    """FPN top-down pass (upsample + add over the levels); the pointer arrays go to `keep`"""
+class FusionState:
+    """Device side of a weighted top-down op (`op["fusion"]`: fast_attention | fast_channel_attention): per fusion the
+    addresses of its two f32 variables (`addr_of(name)`: a buffer that stays where it is — the launches read the weights
+    on the device, so a reload or an optimizer step shows in the next launch or graph replay) and the coefficient block
+    rn_fpn_topdown_fused writes in front of its top-down launches, which the backward launches of the same step read."""
+
+    def __init__(self, lib, op, C, dev, addr_of):
+        self.mode = _C.FUSION_IDS[op["fusion"]]
+        self.names = [tuple(pair) for pair in op["fusion_vars"]]
+        self.coef = [torch.empty((lib.rn_fpn_fusion_coef_bytes(C),), dtype=torch.uint8, device=dev) for _ in self.names]
+        self.w = [(addr_of(lo), addr_of(up)) for lo, up in self.names]
+        self.arrays = (_C.ptr_array_of([w[0] for w in self.w]), _C.ptr_array_of([w[1] for w in self.w]),
+                       _C.ptr_array(self.coef))
+
+
+def topdown_step(lib, op, t, B, keep, fusion=None):
+    """FPN top-down pass (upsample + fusion + activation over the levels); the pointer arrays go to `keep`.  `fusion`:
+    the FusionState of an op with a weighted fusion mode."""
     ins, outs = [t[n] for n in op["ins"]], [t[n] for n in op["outs"]]
     pin, pout = _C.ptr_array(ins), _C.ptr_array(outs)
     keep += [pin, pout]
+    if op.get("fusion"):
+        keep.append(fusion)
+        a = (pin, pout) + fusion.arrays + (len(ins), B, ins[0].shape[1], ins[0].shape[2], ins[0].shape[3],
+                                            _C.ACT_IDS[op["act"]], fusion.mode)
+        return lambda st: _C.check(lib.rn_fpn_topdown_fused(*a, st), "rn_fpn_topdown_fused")
     a = (pin, pout, len(ins), B, ins[0].shape[1], ins[0].shape[2], ins[0].shape[3], _C.ACT_IDS[op["act"]])
     return lambda st: _C.check(lib.rn_fpn_topdown(*a, st), "rn_fpn_topdown")

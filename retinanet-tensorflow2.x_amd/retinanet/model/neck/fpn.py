@@ -1,19 +1,25 @@
 """FPN as static graph ops — retinanet/model/neck/fpn_base.py:54-71 (P6 = maxpool2(BN(conv1x1(C5))), P7 =
 maxpool2(P6)) and retinanet/model/neck/fpn.py:11-107 (lateral 1x1 + BN, top-down `act(P_{l-1} + up2(P_l))` for
 l = max..min+1 — P6 and P5 are refined from above too, P7 gets no activation —, output 3x3 + BN without activation);
-FeatureFusion mode 'sum' (model/layers/feature_fusion.py:41-56), NearestUpsampling2D
-(model/layers/nearest_upsampling.py:19-21).  With `conv_2d.use_seperable_conv` every conv is a SeparableConv2D
+FeatureFusion (model/layers/feature_fusion.py:4-56) in its three modes: 'sum', and the learned 'fast_attention' (two scalars
+per fusion) / 'fast_channel_attention' (two per-channel vectors): `act(P_{l-1} relu(w_l) / s + up2(P_l) relu(w_u) / s)`,
+s = relu(w_l) + relu(w_u) + 1e-4, the variables `<fusion>-lower-level-weight` / `-upper-level-weight` initialised to ones;
+NearestUpsampling2D (model/layers/nearest_upsampling.py:19-21).  With `conv_2d.use_seperable_conv` every conv is a SeparableConv2D
 (fpn_base.py:28-39).  Variable names follow the Keras layer names under the `fpn/` scope."""
 from __future__ import annotations
 
 from retinanet.model.graph import Sym, _conv_or_sep
 
 
+FUSION_MODES = ['sum', 'fast_attention', 'fast_channel_attention']   # FeatureFusion._SUPPORTED_FUSION_MODES
+
+
 class FPN:
     def __init__(self, filters, min_level, max_level, backbone_max_level, fusion_mode="sum", conv_2d_op_params=None,
                  normalization_op_params=None, activation_fn=None, name="fpn", **_):
-        if fusion_mode != "sum":
-            raise NotImplementedError("fusion_mode other than 'sum' is unused by every shipped config")
+        if fusion_mode not in FUSION_MODES:   # feature_fusion.py:9-12
+            raise AssertionError('Requested unsupported mode: {}, available modes are: {}'.format(fusion_mode, FUSION_MODES))
+        self.fusion_mode = fusion_mode
         self.filters, self.min_level, self.max_level = int(filters), int(min_level), int(max_level)
         self.backbone_max_level, self.activation_fn, self.name = int(backbone_max_level), activation_fn, name
         self.separable = bool((conv_2d_op_params or {}).get("use_seperable_conv", False))
@@ -46,8 +52,19 @@ class FPN:
         for level in levels[:-1]:
             Hl, Wl, _, _ = g.tensors[f"fpn_in{level}"]
             g.tensor(f"fpn_td{level}", Hl, Wl, F)
-        g.ops.append(dict(op="topdown", ins=[f"fpn_in{l}" for l in levels],
-                          outs=[f"fpn_td{l}" for l in levels[:-1]] + [f"fpn_in{hi}"], act=act))
+        topdown = dict(op="topdown", ins=[f"fpn_in{l}" for l in levels],
+                       outs=[f"fpn_td{l}" for l in levels[:-1]] + [f"fpn_in{hi}"], act=act)
+        if self.fusion_mode != "sum":
+            # fusion j joins levels[j] and levels[j + 1] (fpn.py:71-79: the layer is keyed by the upper level)
+            shape = (1,) if self.fusion_mode == "fast_attention" else (F,)
+            topdown["fusion"], topdown["fusion_vars"] = self.fusion_mode, []
+            for level in levels[1:]:
+                layer = f"p{level - 1}-in-fusion-with-p{level}-in-upsampled"
+                pair = tuple(f"{pre}{layer}/{layer}-{which}-level-weight" for which in ("lower", "upper"))
+                for v in pair:
+                    g.var_specs[v] = dict(shape=shape, init="const", value=1.0)
+                topdown["fusion_vars"].append(pair)
+        g.ops.append(topdown)
         for level in levels:
             name = f"{pre}p{level}-out-conv-3x3"
             bn = f"{pre}p{level}-out-{bn_tag}"

@@ -33,8 +33,9 @@ import torch
 
 from retinanet import _C
 from .bottleneck import Bottleneck64, fused_blocks
-from .forward import (FoldedConvs, conv_launch_name, conv_problem, dw_problem, half_activations, maxpool_step, split_by_depth,
-                      stem_input, stem_pool_partner, stem_pool_step, stem_problem, tensor_readers, topdown_step)
+from .forward import (FoldedConvs, FusionState, conv_launch_name, conv_problem, dw_problem, half_activations, maxpool_step,
+                      split_by_depth, stem_input, stem_pool_partner, stem_pool_step, stem_problem, tensor_readers,
+                      topdown_step)
 
 _DT = {"bf16": torch.bfloat16, "f32": torch.float32}
 _SEG_DTYPE = np.dtype([("offset", "<i8"), ("size", "<i8"), ("wd", "<i4"), ("bb", "<i4"), ("nb", "<i4"),
@@ -162,6 +163,7 @@ class TrainEngine:
         self._loss_dy = None      # loss_grad_buffers(): the prediction convs' entries of dy_of
         self._dgrad_pack_items = None   # rn_dgrad_pack array over dgrad_packs
         self.drop_connect = True     # stochastic depth of the EfficientNet skip blocks (efficientnet.py:97-113)
+        self.fusion_state = {}       # id(weighted top-down op) -> forward.FusionState (weights, coefficient blocks)
         self.dc_masks = {}           # project conv output -> (f32[B] factors, survival_prob)
         self.dc_all = self.dc_p = None
         self.dc_generator = torch.Generator(device=self.dev)
@@ -262,6 +264,13 @@ class TrainEngine:
         for sname in getattr(g, "ses", {}):
             self.var_kind[sname + "/conv2d/kernel"] = ("se1", sname)
             self.var_kind[sname + "/conv2d_1/kernel"] = ("se2", sname)
+        # FeatureFusion's weights are decayed too: the reference decays every trainable variable of a layer that is no
+        # conv layer whose name contains 'kernel' or 'weight' (executor.py:320-323)
+        for o in self.ops:
+            if o["op"] == "topdown" and o.get("fusion"):
+                for j, pair in enumerate(o["fusion_vars"]):
+                    for name in pair:
+                        self.var_kind[name] = ("fusion", j)
 
     def _kvar(self, op):
         if op["op"] == "dwconv":
@@ -289,7 +298,12 @@ class TrainEngine:
             elif kind == "maxpool":
                 self.requires[op["out"]] = self.requires[op["inp"]]
             elif kind == "topdown":
-                r = any(self.requires[i] for i in op["ins"])
+                live = [n for pair in op.get("fusion_vars", ()) for n in pair if n not in self.frozen]
+                dead = [i for i in op["ins"] if not self.requires[i]]
+                if live and dead:   # the weighted backward level writes din of every level: such an input has no buffer
+                    raise NotImplementedError(f"fusion weights {live[0]} .. train while the top-down inputs {dead} are "
+                                              "frozen down to the image: freeze the fusion weights with them")
+                r = any(self.requires[i] for i in op["ins"]) or bool(live)
                 for o in op["outs"]:
                     self.requires[o] = r or self.requires.get(o, False)
             elif kind == "balance":
@@ -592,6 +606,9 @@ class TrainEngine:
         for op in self.ops:
             if op["op"] in ("conv", "stem") and not self._conv_trainable(op) and op["out"] not in self._bneck_skip:
                 self.folded.load(self.model.variables, op)
+            elif op["op"] == "topdown" and op.get("fusion"):   # frozen fusion weights: f32 copies at stable addresses
+                for name in (n for pair in op["fusion_vars"] for n in pair if n in self.frozen):
+                    self.folded.stable(name, self.model.variables[name].to(self.dev, torch.float32).reshape(-1).clone())
         for fb in self.bneck.values():
             fb.load(self.model.variables, self.eps)
 
@@ -945,7 +962,12 @@ class TrainEngine:
                     continue
                 self.fwd_steps.append(maxpool_step(lib, op, self.t, B))
             elif kind == "topdown":
-                self.fwd_steps.append(topdown_step(lib, op, self.t, B, self._keep))
+                fusion = None
+                if op.get("fusion"):   # live weights are read where they live: the flat parameter arena
+                    fusion = self.fusion_state[id(op)] = FusionState(
+                        lib, op, self.t[op["ins"][0]].shape[3], self.dev,
+                        lambda n: self._pview(n).data_ptr() if n in self.p_off else self.folded.packed[n].data_ptr())
+                self.fwd_steps.append(topdown_step(lib, op, self.t, B, self._keep, fusion))
             elif kind == "balance":
                 ts = [self.t[n] for n in op["tensors"]]
                 outs = [self.bal_out[n] for n in op["tensors"]]
@@ -1071,6 +1093,9 @@ class TrainEngine:
                     raise NotImplementedError(f"backward of the top-down op {op['outs'][0]} .. {op['outs'][-1]} with "
                                               "activation 'swish' is not built (relu / relu6 / none are)")
                 act = _C.ACT_IDS[op["act"]]
+                if op.get("fusion"):
+                    self._plan_fused_topdown_backward(op, act, mark)
+                    continue
                 prev = None
                 for l in range(L):
                     dout = self.grad[op["outs"][l]]
@@ -1108,6 +1133,45 @@ class TrainEngine:
                 arr[i].w_ohwi, arr[i].w_packed = mptr, buf.data_ptr()
                 arr[i].R, arr[i].S, arr[i].Cin, arr[i].Cout, arr[i].Cout_pad, arr[i].pad_ = k, k, cin, cout, cw, mode
             self._dgrad_pack_items = arr
+
+    def _plan_fused_topdown_backward(self, op, act, mark):
+        """Backward of a weighted top-down op, finest level first: per level one rn_fpn_fused_bwd_level (the gated gradient
+        g overwrites dout — nothing reads dout afterwards —, din, stage 1 of the two weight-gradient sums) and one
+        rn_fpn_fused_bwd_finalize that writes dw_lower / dw_upper into the gradient arena.  Both run on the main stream, in
+        order, so the arena is complete before anything that follows the backward pass reads it; `writes` tells the
+        bucketed all-reduce which variables the step completes."""
+        lib, B, fus = self.lib, self.B, self.fusion_state[id(op)]
+        L = len(op["ins"])
+        prev_g = prev_coef = None
+        for l in range(L):
+            dout, din = self.grad[op["outs"][l]], self.grad[op["ins"][l]]
+            mark(op["ins"][l])
+            _, H, W, C = dout.shape
+            if l == L - 1:
+                a = (dout.data_ptr(), prev_g, prev_coef, None, None, None, None, None, din.data_ptr(), None, 0, B, H, W, C,
+                     _C.RN_ACT_NONE)
+                self.bwd_steps.append(lambda st, a=a: _C.check(lib.rn_fpn_fused_bwd_level(*a, st), "fused_topdown_bwd"))
+                break
+            ws = torch.empty((lib.rn_fpn_fused_bwd_workspace_bytes(B, H, W, C),), dtype=torch.uint8, device=self.dev)
+            coef = fus.coef[l].data_ptr()
+            a = (dout.data_ptr(), prev_g, prev_coef, self.t[op["outs"][l]].data_ptr(), self.t[op["ins"][l]].data_ptr(),
+                 self.t[op["outs"][l + 1]].data_ptr(), coef, dout.data_ptr(), din.data_ptr(), ws.data_ptr(), ws.numel(),
+                 B, H, W, C, act)
+            live = [n for n in fus.names[l] if n in self.p_off]
+            # a frozen weight's gradient goes to a scratch nobody reads
+            dw = [self._pview(n, self.G) if n in self.p_off else torch.empty_like(self.folded.packed[n])
+                  for n in fus.names[l]]
+            f = (ws.data_ptr(), ws.numel(), B, H, W, C, fus.w[l][0], fus.w[l][1], coef, fus.mode, None,
+                 dw[0].data_ptr(), dw[1].data_ptr())
+            self._keep += [ws, dw]
+
+            def level(st, a=a, f=f, finalize=bool(live)):
+                _C.check(lib.rn_fpn_fused_bwd_level(*a, st), "fused_topdown_bwd")
+                if finalize:
+                    _C.check(lib.rn_fpn_fused_bwd_finalize(*f, st), "fused_topdown_bwd_finalize")
+            level.writes = live
+            self.bwd_steps.append(level)
+            prev_g, prev_coef = dout.data_ptr(), coef
 
     def set_wgrad_cap(self, on):
         """The CU cap of the weight-gradient launches (see _plan_conv_backward) on / off: with the chip to themselves
