@@ -79,6 +79,14 @@ int rn_anchor_match_encode(const float* anchors, int64_t A, const float* gt_boxe
                            const float* box_variance, int32_t* matches, float* class_targets,
                            float* box_targets, float* num_positives, void* workspace, size_t workspace_bytes,
                            void* stream);
+/* The same matching and targets (bit for bit) plus the auxiliary head's IoU targets (label_encoder.py:96-97):
+ * iou_targets f32[B,A] = IoU(anchor, matched gt box) where matches > -1, else -1 — compute_iou's arithmetic, one
+ * rounding per op.  The matched box is already gathered for the box target: no further pass over the ground truth. */
+int rn_anchor_match_encode_iou(const float* anchors, int64_t A, const float* gt_boxes, const float* gt_classes,
+                               const int32_t* gt_counts, int B, int Gmax, float match_iou, float ignore_iou,
+                               const float* box_variance, int32_t* matches, float* class_targets,
+                               float* box_targets, float* num_positives, float* iou_targets, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * a9  RetinaNetLoss / ClassLoss / FocalLossV1 / BoxLoss
@@ -113,6 +121,26 @@ int rn_retinanet_loss_fwd_bwd_bf16(const float* const* class_logits, const float
                                    float label_smoothing, float delta, float box_loss_weight,
                                    float class_loss_weight, float grad_scale, float* losses, void* workspace,
                                    size_t workspace_bytes, void* stream);
+/* IouPredictionLoss (loss_impl.py:108-131, retinanet_loss.py:72-82): sum-reduced MSE of the auxiliary head's raw f32
+ * predictions iou_preds[l] f32[B*H_l*W_l][pred_pix_stride] (the anchors_per_location live channels in front: the
+ * prediction conv writes a channel count padded to a multiple of 4; dense maps pass anchors_per_location) against iou_targets f32[B, A] (rn_anchor_match_encode_iou) where target > -1,
+ * over all levels in one launch, divided by normalizer (device f32[1]).
+ * out: device f32[2] = {iou-prediction-loss, weighted_in[0] + auxillary_loss_weight * iou-prediction-loss}
+ * (weighted_in: device f32[1], e.g. losses + 2 of rn_retinanet_loss_fwd_bwd enqueued before on the same stream; NULL
+ * = 0).  Gradient 2 (pred - target) * (auxillary_loss_weight * grad_scale / normalizer), exactly 0 where target <= -1:
+ * d_iou_preds[l] dense f32[B, n_l] (NULL array: no backward), or — _bf16 — the 16-bit type of the build straight into
+ * d_iou_bf16[l] [B*H_l*W_l][pix_stride] with the anchors_per_location live channels in front (pad channels are not
+ * touched).  Deterministic two-stage sums (no float atomics).  workspace: rn_iou_loss_workspace_bytes(B, A). */
+size_t rn_iou_loss_workspace_bytes(int B, int64_t A);
+int rn_iou_loss_fwd_bwd(const float* const* iou_preds, int pred_pix_stride, int anchors_per_location,
+                        float* const* d_iou_preds, const int64_t* level_offsets, int num_levels, int B, const float* iou_targets, const float* normalizer,
+                        const float* weighted_in, float auxillary_loss_weight, float grad_scale, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int rn_iou_loss_fwd_bwd_bf16(const float* const* iou_preds, int pred_pix_stride, void* const* d_iou_bf16, int pix_stride,
+                             int anchors_per_location, const int64_t* level_offsets, int num_levels, int B,
+                             const float* iou_targets, const float* normalizer, const float* weighted_in,
+                             float auxillary_loss_weight, float grad_scale, float* out, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * a11+a12  FuseDetections + TransformBoxesAndScores

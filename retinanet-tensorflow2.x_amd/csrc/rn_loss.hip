@@ -475,3 +475,148 @@ extern "C" int rn_retinanet_loss_fwd_bwd_bf16(const float* const* class_logits, 
                      normalizer, alpha, gamma, label_smoothing, delta, box_loss_weight, class_loss_weight, grad_scale,
                      losses, workspace, workspace_bytes, stream);
 }
+
+// ---- IoU-prediction loss of the auxiliary head (loss_impl.py:108-131, retinanet_loss.py:72-82) ------------------------
+// Per anchor with IoU target t (rn_anchor_match_encode_iou: -1 on every non-positive anchor) and raw f32 prediction x
+// (no sigmoid): sample_weight = t > -1, L = w (x - t)^2 summed over anchors, levels and images, divided by the same
+// normalizer as the other two losses; dL/dx = 2 (x - t) * (auxillary_loss_weight * grad_scale / normalizer), exactly 0
+// where t <= -1.  One thread per (image, anchor) over all levels — the Huber kernel's indexing with one channel —, the
+// same two-stage sums (per-thread fp32 -> per-block double partial -> one wavefront adds the partials in index order),
+// so the sum is bit-identical from run to run.  Algorithmic bytes 12 per anchor (prediction + target + f32 gradient).
+struct IouLevels {
+  int num_levels, na, stride16, pstride;   // pstride: f32 elements between the pixels of a prediction map (>= na)
+  const float* pred[RN_LOSS_MAX_LEVELS];
+  float* dpred[RN_LOSS_MAX_LEVELS];
+  uint16_t* dpred16[RN_LOSS_MAX_LEVELS];   // write_grad == 2: [B*H*W][stride16], the level's na live channels in front
+  long long off[RN_LOSS_MAX_LEVELS + 1];
+};
+
+__global__ void __launch_bounds__(RN_LOSS_THREADS)
+iou_mse_kernel(IouLevels lv, int B, long long A, const float* __restrict__ iou_targets,
+               const float* __restrict__ normalizer, float gscale, int write_grad, double* __restrict__ partials) {
+  const long long total = (long long)B * A;
+  float acc = 0.0f;
+  const float gs = gscale / normalizer[0];
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / A;
+    const long long a = i - b * A;
+    int l = 0;
+    while (l + 1 < lv.num_levels && a >= lv.off[l + 1]) ++l;
+    const long long n_l = lv.off[l + 1] - lv.off[l];
+    const long long row = b * n_l + (a - lv.off[l]);
+    const float t = iou_targets[i];
+    const bool live = t > -1.0f;
+    const long long pix = row / lv.na;          // rows are (image, pixel, anchor): na anchors per pixel
+    const int ch = (int)(row - pix * lv.na);
+    const float e = lv.pred[l][pix * lv.pstride + ch] - t;
+    if (live) acc += e * e;
+    const float g = live ? (2.0f * e) * gs : 0.0f;
+    if (write_grad == 1) {
+      lv.dpred[l][row] = g;
+    } else if (write_grad == 2) {
+      lv.dpred16[l][pix * lv.stride16 + ch] = rn_f32_to_bf16(g);
+    }
+  }
+  __shared__ double sred[RN_LOSS_THREADS / 64];
+  double d = rn_wave_sum_d((double)acc);
+  if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = d;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int w = 0; w < RN_LOSS_THREADS / 64; ++w) s += sred[w];
+    partials[blockIdx.x] = s;
+  }
+}
+
+// one wavefront, as loss_finalize; out[0] = iou-prediction-loss, out[1] = weighted_in + w * out[0]
+__global__ void iou_loss_finalize(const double* __restrict__ part, int n, const float* __restrict__ normalizer,
+                                  const float* __restrict__ weighted_in, float aux_w, float* __restrict__ out) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 64) s += part[i];
+  s = rn_wave_sum_d(s);
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const float iou_loss = (float)s / normalizer[0];
+    out[0] = iou_loss;
+    out[1] = (weighted_in ? weighted_in[0] : 0.0f) + aux_w * iou_loss;
+  }
+}
+
+extern "C" size_t rn_iou_loss_workspace_bytes(int B, int64_t A) {
+  (void)B; (void)A;
+  return 2048 * sizeof(double);
+}
+
+static int iou_loss_launch(const char* who, const float* const* iou_preds, int pred_pix_stride,
+                           float* const* d_iou_preds, void* const* d_iou_16, int pix_stride, int anchors_per_location,
+                           const int64_t* level_offsets, int num_levels, int B, const float* iou_targets,
+                           const float* normalizer, const float* weighted_in, float auxillary_loss_weight,
+                           float grad_scale, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  RN_CHECK_ARG(iou_preds && level_offsets && iou_targets && normalizer && out, "%s: null argument", who);
+  RN_CHECK_ARG(num_levels >= 1 && num_levels <= RN_LOSS_MAX_LEVELS && B > 0, "%s: bad num_levels=%d B=%d", who,
+               num_levels, B);
+  if (!workspace || workspace_bytes < rn_iou_loss_workspace_bytes(B, 0)) {
+    rn_set_error("%s: workspace too small", who);
+    return RN_ENOMEM;
+  }
+  const int write_grad = d_iou_16 ? 2 : d_iou_preds ? 1 : 0;
+  IouLevels lv = {};
+  lv.num_levels = num_levels;
+  lv.na = anchors_per_location;
+  lv.stride16 = pix_stride;
+  lv.pstride = pred_pix_stride;
+  RN_CHECK_ARG(anchors_per_location > 0 && pred_pix_stride >= anchors_per_location,
+               "%s: bad prediction stride %d for %d anchors per location", who, pred_pix_stride, anchors_per_location);
+  if (write_grad == 2)
+    RN_CHECK_ARG(pix_stride >= anchors_per_location, "%s: bad gradient stride %d for %d anchors per location", who,
+                 pix_stride, anchors_per_location);
+  RN_CHECK_ARG(level_offsets[0] == 0, "%s: level_offsets[0] must be 0", who);
+  lv.off[0] = 0;
+  for (int l = 0; l < num_levels; ++l) {
+    const long long n_l = level_offsets[l + 1] - level_offsets[l];
+    RN_CHECK_ARG(n_l > 0, "%s: empty level %d", who, l);
+    RN_CHECK_ARG(iou_preds[l], "%s: level %d: null predictions", who, l);
+    lv.pred[l] = iou_preds[l];
+    lv.dpred[l] = write_grad == 1 ? d_iou_preds[l] : nullptr;
+    lv.dpred16[l] = write_grad == 2 ? (uint16_t*)d_iou_16[l] : nullptr;
+    if (write_grad == 1) RN_CHECK_ARG(lv.dpred[l], "%s: level %d: null gradient output", who, l);
+    RN_CHECK_ARG(n_l % anchors_per_location == 0, "%s: level %d: anchors not a multiple of %d", who, l,
+                 anchors_per_location);
+    if (write_grad == 2) RN_CHECK_ARG(lv.dpred16[l], "%s: level %d: null gradient output", who, l);
+    lv.off[l + 1] = level_offsets[l + 1];
+  }
+  const long long A = lv.off[num_levels];
+  hipStream_t st = (hipStream_t)stream;
+  double* part = (double*)workspace;
+  const int nb = loss_blocks((long long)B * A);
+  hipLaunchKernelGGL(iou_mse_kernel, dim3(nb), dim3(RN_LOSS_THREADS), 0, st, lv, B, A, iou_targets, normalizer,
+                     auxillary_loss_weight * grad_scale, write_grad, part);
+  RN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(iou_loss_finalize, dim3(1), dim3(64), 0, st, part, nb, normalizer, weighted_in,
+                     auxillary_loss_weight, out);
+  RN_CHECK_LAUNCH();
+  return RN_OK;
+}
+
+extern "C" int rn_iou_loss_fwd_bwd(const float* const* iou_preds, int pred_pix_stride, int anchors_per_location,
+                                   float* const* d_iou_preds, const int64_t* level_offsets, int num_levels, int B, const float* iou_targets,
+                                   const float* normalizer, const float* weighted_in, float auxillary_loss_weight,
+                                   float grad_scale, float* out, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+  return iou_loss_launch("rn_iou_loss_fwd_bwd", iou_preds, pred_pix_stride, d_iou_preds, nullptr, 0,
+                         anchors_per_location, level_offsets, num_levels, B,
+                         iou_targets, normalizer, weighted_in, auxillary_loss_weight, grad_scale, out, workspace,
+                         workspace_bytes, stream);
+}
+
+extern "C" int rn_iou_loss_fwd_bwd_bf16(const float* const* iou_preds, int pred_pix_stride,
+                                        void* const* d_iou_bf16, int pix_stride,
+                                        int anchors_per_location, const int64_t* level_offsets, int num_levels, int B,
+                                        const float* iou_targets, const float* normalizer, const float* weighted_in,
+                                        float auxillary_loss_weight, float grad_scale, float* out, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  RN_CHECK_ARG(d_iou_bf16, "rn_iou_loss_fwd_bwd_bf16: null gradient outputs");
+  return iou_loss_launch("rn_iou_loss_fwd_bwd_bf16", iou_preds, pred_pix_stride, nullptr, d_iou_bf16, pix_stride, anchors_per_location,
+                         level_offsets, num_levels, B, iou_targets, normalizer, weighted_in, auxillary_loss_weight,
+                         grad_scale, out, workspace, workspace_bytes, stream);
+}

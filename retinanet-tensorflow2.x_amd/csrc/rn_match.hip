@@ -110,12 +110,18 @@ match_pass1(const float4* __restrict__ anchors, long long A, const float4* __res
     if (sbest[g] != 0ull) atomicMax(&best[(long long)b * Gmax + g], sbest[g]);
 }
 
+// IOU: also iou_targets[b][a] = IoU(anchor, matched GT) for a positive anchor, -1 otherwise (label_encoder.py:96-97:
+// compute_iou(..., pair_wise=False) on the gathered boxes, then where(matches > -1, ., -1)).  The matched GT and the
+// anchor are already in registers for the box target, so this is one more iou_cxcywh per positive anchor (in the branch
+// the box target's logarithms already take) — the same function, hence the same roundings, as the one pass 1 matched
+// with — and 4 more bytes written per anchor.
+template <bool IOU>
 __global__ void __launch_bounds__(RN_MATCH_THREADS)
 match_pass2(const float4* __restrict__ anchors, long long A, const float4* __restrict__ gt_boxes,
             const float* __restrict__ gt_classes, const int* __restrict__ gt_counts, int Gmax,
             const unsigned long long* __restrict__ best, int* __restrict__ matches,
             float* __restrict__ class_targets, float4* __restrict__ box_targets, int* __restrict__ pos_count,
-            float4 inv_var, int use_var) {
+            float4 inv_var, int use_var, float* __restrict__ iou_targets) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned int* sbest = (unsigned int*)smem;
   int& s_pos = *(int*)(smem + (size_t)(Gmax < 1 ? 1 : Gmax) * 4);
@@ -146,6 +152,7 @@ match_pass2(const float4* __restrict__ anchors, long long A, const float4* __res
       cls = gt_classes[(long long)b * Gmax + m];
     }
     float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+    float iou_t = -1.0f;
     if (m >= 0) {
       const float eps = 1e-8f;  // label_encoder.py:57-58, applied to all four coordinates
       const float gx = fmaxf(gt.x, eps), gy = fmaxf(gt.y, eps), gw = fmaxf(gt.z, eps), gh = fmaxf(gt.w, eps);
@@ -159,11 +166,13 @@ match_pass2(const float4* __restrict__ anchors, long long A, const float4* __res
         t.z = t.z / inv_var.z;
         t.w = t.w / inv_var.w;
       }
+      if (IOU) iou_t = iou_cxcywh(gt, an);   // inside the positives' branch: a wave without a positive anchor skips it
       ++positives;
     }
     matches[(long long)b * A + a_idx] = m;
     class_targets[(long long)b * A + a_idx] = cls;
     box_targets[(long long)b * A + a_idx] = t;
+    if (IOU) iou_targets[(long long)b * A + a_idx] = iou_t;
   }
   // positives: integer sums (deterministic); the float conversion is match_finalize's
   if (positives) atomicAdd(&s_pos, positives);
@@ -182,21 +191,19 @@ extern "C" size_t rn_match_workspace_bytes(int B, int Gmax) {
   return rn_align_up((size_t)B * Gmax * 8, 256) + rn_align_up((size_t)B * 4, 256) * 2;
 }
 
-extern "C" int rn_anchor_match_encode(const float* anchors, int64_t A, const float* gt_boxes,
-                                      const float* gt_classes, const int32_t* gt_counts, int B, int Gmax,
-                                      float match_iou, float ignore_iou, const float* box_variance,
-                                      int32_t* matches, float* class_targets, float* box_targets,
-                                      float* num_positives, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
+static int match_launch(const char* who, const float* anchors, int64_t A, const float* gt_boxes,
+                        const float* gt_classes, const int32_t* gt_counts, int B, int Gmax, float match_iou,
+                        float ignore_iou, const float* box_variance, int32_t* matches, float* class_targets,
+                        float* box_targets, float* num_positives, float* iou_targets, void* workspace,
+                        size_t workspace_bytes, void* stream) {
   RN_CHECK_ARG(anchors && gt_counts && matches && class_targets && box_targets && num_positives,
-               "rn_anchor_match_encode: null argument");
-  RN_CHECK_ARG(A > 0 && A < (1ll << 31) && B > 0, "rn_anchor_match_encode: bad A=%lld B=%d", (long long)A, B);
-  RN_CHECK_ARG(Gmax >= 0 && Gmax <= RN_MATCH_GMAX, "rn_anchor_match_encode: Gmax=%d outside 0..%d", Gmax,
-               RN_MATCH_GMAX);
-  RN_CHECK_ARG(Gmax == 0 || (gt_boxes && gt_classes), "rn_anchor_match_encode: null gt arrays");
+               "%s: null argument", who);
+  RN_CHECK_ARG(A > 0 && A < (1ll << 31) && B > 0, "%s: bad A=%lld B=%d", who, (long long)A, B);
+  RN_CHECK_ARG(Gmax >= 0 && Gmax <= RN_MATCH_GMAX, "%s: Gmax=%d outside 0..%d", who, Gmax, RN_MATCH_GMAX);
+  RN_CHECK_ARG(Gmax == 0 || (gt_boxes && gt_classes), "%s: null gt arrays", who);
   const size_t need = rn_match_workspace_bytes(B, Gmax);
   if (workspace_bytes < need || !workspace) {
-    rn_set_error("rn_anchor_match_encode: workspace %zu < %zu", workspace_bytes, need);
+    rn_set_error("%s: workspace %zu < %zu", who, workspace_bytes, need);
     return RN_ENOMEM;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -212,11 +219,39 @@ extern "C" int rn_anchor_match_encode(const float* anchors, int64_t A, const flo
   RN_CHECK_LAUNCH();
   float4 var = make_float4(1.f, 1.f, 1.f, 1.f);
   if (box_variance) var = make_float4(box_variance[0], box_variance[1], box_variance[2], box_variance[3]);
-  hipLaunchKernelGGL(match_pass2, grid, dim3(RN_MATCH_THREADS), (size_t)Gm * 4 + 16, st, (const float4*)anchors,
-                     (long long)A, (const float4*)gt_boxes, gt_classes, gt_counts, Gmax, best, matches,
-                     class_targets, (float4*)box_targets, pos, var, box_variance ? 1 : 0);
+  if (iou_targets)
+    hipLaunchKernelGGL(match_pass2<true>, grid, dim3(RN_MATCH_THREADS), (size_t)Gm * 4 + 16, st,
+                       (const float4*)anchors, (long long)A, (const float4*)gt_boxes, gt_classes, gt_counts, Gmax, best,
+                       matches, class_targets, (float4*)box_targets, pos, var, box_variance ? 1 : 0, iou_targets);
+  else
+    hipLaunchKernelGGL(match_pass2<false>, grid, dim3(RN_MATCH_THREADS), (size_t)Gm * 4 + 16, st,
+                       (const float4*)anchors, (long long)A, (const float4*)gt_boxes, gt_classes, gt_counts, Gmax, best,
+                       matches, class_targets, (float4*)box_targets, pos, var, box_variance ? 1 : 0, (float*)nullptr);
   RN_CHECK_LAUNCH();
   hipLaunchKernelGGL(match_finalize, dim3((unsigned)rn_cdiv(B, 256)), dim3(256), 0, st, pos, num_positives, B);
   RN_CHECK_LAUNCH();
   return RN_OK;
+}
+
+extern "C" int rn_anchor_match_encode(const float* anchors, int64_t A, const float* gt_boxes,
+                                      const float* gt_classes, const int32_t* gt_counts, int B, int Gmax,
+                                      float match_iou, float ignore_iou, const float* box_variance,
+                                      int32_t* matches, float* class_targets, float* box_targets,
+                                      float* num_positives, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return match_launch("rn_anchor_match_encode", anchors, A, gt_boxes, gt_classes, gt_counts, B, Gmax, match_iou,
+                      ignore_iou, box_variance, matches, class_targets, box_targets, num_positives, nullptr, workspace,
+                      workspace_bytes, stream);
+}
+
+extern "C" int rn_anchor_match_encode_iou(const float* anchors, int64_t A, const float* gt_boxes,
+                                          const float* gt_classes, const int32_t* gt_counts, int B, int Gmax,
+                                          float match_iou, float ignore_iou, const float* box_variance,
+                                          int32_t* matches, float* class_targets, float* box_targets,
+                                          float* num_positives, float* iou_targets, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  RN_CHECK_ARG(iou_targets, "rn_anchor_match_encode_iou: null iou_targets");
+  return match_launch("rn_anchor_match_encode_iou", anchors, A, gt_boxes, gt_classes, gt_counts, B, Gmax, match_iou,
+                      ignore_iou, box_variance, matches, class_targets, box_targets, num_positives, iou_targets,
+                      workspace, workspace_bytes, stream);
 }

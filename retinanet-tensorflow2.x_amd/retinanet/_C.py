@@ -22,7 +22,7 @@ RN_ACT_NONE, RN_ACT_RELU, RN_ACT_RELU6, RN_ACT_SWISH = 0, 1, 2, 3
 RN_FUSION_FAST_ATTENTION, RN_FUSION_FAST_CHANNEL_ATTENTION = 1, 2
 FUSION_IDS = {"fast_attention": RN_FUSION_FAST_ATTENTION, "fast_channel_attention": RN_FUSION_FAST_CHANNEL_ATTENTION}
 RN_CONV_MAX_SEGMENTS = 10
-ABI_VERSION = 9
+ABI_VERSION = 10
 # f32 kernels of the dtype=float32 prediction convs (detection_head.py:80-88) as split-bf16 planes (rn_conv_segment.w_terms)
 PRED_W_TERMS = int(os.environ.get("RNET_PRED_W_TERMS", "2"))
 ACT_IDS = {None: RN_ACT_NONE, "none": RN_ACT_NONE, "relu": RN_ACT_RELU, "relu6": RN_ACT_RELU6,
@@ -134,7 +134,15 @@ _SIGNATURES = {
     "rn_anchor_match_encode": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
                                        c_float, POINTER(c_float), c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),
+    "rn_anchor_match_encode_iou": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
+                                           c_float, POINTER(c_float), c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_size_t, c_void_p]),
     "rn_loss_workspace_bytes": (c_size_t, [c_int, c_int64, c_int]),
+    "rn_iou_loss_workspace_bytes": (c_size_t, [c_int, c_int64]),
+    "rn_iou_loss_fwd_bwd": (c_int, [_PP, c_int, c_int, _PP, POINTER(c_int64), c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
+                                    c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rn_iou_loss_fwd_bwd_bf16": (c_int, [_PP, c_int, _PP, c_int, c_int, POINTER(c_int64), c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rn_retinanet_loss_fwd_bwd": (c_int, [_PP, _PP, _PP, _PP, POINTER(c_int64), c_int, c_int, c_int, c_void_p,
                                           c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float,
                                           c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -3,7 +3,7 @@
 The reference encodes one sample at a time inside tf.data on the host; here a whole batch of
 padded ground truth is matched and encoded in two HBM-bound launches (rn_anchor_match_encode).
 `encode_batch` returns the reference's target dict (`class-targets`, `box-targets` per level,
-`num-positives`) as zero-copy views of the flattened outputs, plus the flattened tensors
+`num-positives`, and `iou-targets` per level when the auxiliary head is on) as zero-copy views of the flattened outputs, plus the flattened tensors
 themselves under `_flat` for the fused loss kernel.
 """
 from __future__ import annotations
@@ -26,6 +26,8 @@ class LabelEncoder:
                                                      params.anchor_params, device=device)
         self._params = params
         self._device = self.anchors.boxes.device
+        # architecture.auxillary_head.use_auxillary_head (label_encoder.py:102-103): also emit `iou-targets`
+        self._iou_targets = bool(params.architecture.auxillary_head.use_auxillary_head)
         self._ws = None
 
     def encode_batch(self, gt_boxes, gt_classes, gt_counts):
@@ -47,15 +49,23 @@ class LabelEncoder:
         var = None
         if self.encoder_params.scale_box_targets:
             var = _C.f32_array(self.encoder_params.box_variance)
-        with torch.cuda.device(dev):
-            _C.check(lib.rn_anchor_match_encode(
-                _C.ptr(self.anchors.boxes), A, _C.ptr(gt_boxes) if Gmax else None,
+        iou_t = torch.empty((B, A), dtype=torch.float32, device=dev) if self._iou_targets else None
+        head = (_C.ptr(self.anchors.boxes), A, _C.ptr(gt_boxes) if Gmax else None,
                 _C.ptr(gt_classes) if Gmax else None, _C.ptr(gt_counts), B, Gmax,
                 float(self.encoder_params.match_iou), float(self.encoder_params.ignore_iou), var,
-                _C.ptr(matches), _C.ptr(cls_t), _C.ptr(box_t), _C.ptr(num_pos), _C.ptr(self._ws),
-                self._ws.numel(), _C.current_stream()), "rn_anchor_match_encode")
+                _C.ptr(matches), _C.ptr(cls_t), _C.ptr(box_t), _C.ptr(num_pos))
+        with torch.cuda.device(dev):
+            if iou_t is None:
+                _C.check(lib.rn_anchor_match_encode(*head, _C.ptr(self._ws), self._ws.numel(), _C.current_stream()),
+                         "rn_anchor_match_encode")
+            else:
+                _C.check(lib.rn_anchor_match_encode_iou(*head, _C.ptr(iou_t), _C.ptr(self._ws), self._ws.numel(),
+                                                        _C.current_stream()), "rn_anchor_match_encode_iou")
         targets = {"class-targets": {}, "box-targets": {}, "num-positives": num_pos,
                    "_flat": {"matches": matches, "class-targets": cls_t, "box-targets": box_t}}
+        if iou_t is not None:
+            targets["iou-targets"] = {}
+            targets["_flat"]["iou-targets"] = iou_t
         bnd = self.anchors.anchor_boundaries
         na = self.anchors.num_anchors_per_location
         for i, level in enumerate(range(self._min_level, self._max_level + 1)):
@@ -63,6 +73,8 @@ class LabelEncoder:
             fw = int(math.ceil(self.input_shape[1] / 2 ** level))
             targets["class-targets"][str(level)] = cls_t[:, bnd[i]:bnd[i + 1]].reshape(B, fh, fw, na)
             targets["box-targets"][str(level)] = box_t[:, bnd[i]:bnd[i + 1]].reshape(B, fh, fw, 4 * na)
+            if iou_t is not None:
+                targets["iou-targets"][str(level)] = iou_t[:, bnd[i]:bnd[i + 1]].reshape(B, fh, fw, na)
         return targets
 
     def encode_sample(self, gt_boxes, cls_ids):
@@ -75,4 +87,6 @@ class LabelEncoder:
         out = {"class-targets": {k: v[0] for k, v in t["class-targets"].items()},
                "box-targets": {k: v[0] for k, v in t["box-targets"].items()},
                "num-positives": t["num-positives"][0], "_flat": t["_flat"]}
+        if "iou-targets" in t:
+            out["iou-targets"] = {k: v[0] for k, v in t["iou-targets"].items()}
         return out

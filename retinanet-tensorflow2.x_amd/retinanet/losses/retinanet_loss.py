@@ -44,7 +44,10 @@ class RetinaNetLoss:
         the caller (the training engine folds that scalar into its first SyncBN message) — else computed here.
         grads_bf16 = {"class-predictions": {level: bf16[B,H,W,stride]}, "box-predictions": {...}}: write the
         gradients as bf16 into these (channel-padded) tensors instead of fp32 `self.grads` — the training engine
-        passes the dy tensors of the prediction convs, so no fp32 gradient is materialised."""
+        passes the dy tensors of the prediction convs, so no fp32 gradient is materialised.
+        With `iou-predictions` among the predictions (the auxiliary head, retinanet_loss.py:72-82) a second launch set
+        adds the IoU-prediction loss: `iou-prediction-loss` and the updated `weighted-loss` are device scalars, the
+        gradients go to `.grads["iou-predictions"]` / `grads_bf16["iou-predictions"]`."""
         lib = _C.lib()
         cls_pred = predictions["class-predictions"]
         box_pred = predictions["box-predictions"]
@@ -113,5 +116,69 @@ class RetinaNetLoss:
             self.grads = None
         elif compute_grads:
             self.grads = {"class-predictions": dict(zip(levels, dcl)), "box-predictions": dict(zip(levels, dbl))}
-        return {"box-loss": out[0], "class-loss": out[1], "weighted-loss": out[2],
-                "num-anchors-matched": out[3], "iou-prediction-loss": 0.0}
+        losses = {"box-loss": out[0], "class-loss": out[1], "weighted-loss": out[2],
+                  "num-anchors-matched": out[3], "iou-prediction-loss": 0.0}
+        if "iou-predictions" in predictions:
+            iou = self._iou_loss(flat, predictions["iou-predictions"], levels, offs, B, normalizer, out[2:3],
+                                 float(grad_scale), compute_grads, grads_bf16 if bf16_out else None)
+            losses["iou-prediction-loss"], losses["weighted-loss"] = iou[0], iou[1]
+        return losses
+
+    def _iou_loss(self, flat, iou_pred, levels, offs, B, normalizer, weighted, grad_scale, compute_grads, grads_bf16):
+        """IouPredictionLoss (loss_impl.py:108-131) over all levels: f32[2] = {iou-prediction-loss, weighted-loss +
+        auxillary_loss_weight * iou-prediction-loss}, on the device; nothing here waits for the GPU."""
+        if "iou-targets" not in flat:
+            raise KeyError("the predictions hold `iou-predictions` but the targets no `iou-targets`: encode them with "
+                           "architecture.auxillary_head.use_auxillary_head on")
+        iou_t = flat["iou-targets"]
+        dev = iou_t.device
+        na = iou_pred[levels[0]].shape[-1]
+        pl, strides = [], set()
+        for i, lv in enumerate(levels):
+            p = iou_pred[lv]
+            if p.dtype != torch.float32:
+                raise TypeError("predictions must be float32 (the reference's prediction convs are fp32)")
+            if p.dim() != 4 or p.shape[-1] != na or p.numel() != B * (offs[i + 1] - offs[i]):
+                raise ValueError(f"iou-predictions of level {lv}: shape {tuple(p.shape)} for "
+                                 f"{offs[i + 1] - offs[i]} anchors per image, {na} per location")
+            # the engines hand out the first `na` channels of the map their prediction conv writes (a multiple of 4
+            # channels): such a view is read in place through its pixel stride
+            base = p._base
+            if (not p.is_contiguous() and base is not None and base.is_contiguous() and base.dim() == 4
+                    and base.shape[:3] == p.shape[:3] and base.data_ptr() == p.data_ptr()):
+                strides.add(int(base.shape[3]))
+            else:
+                p = p.contiguous()
+                strides.add(na)
+            pl.append(p)
+        if len(strides) > 1:
+            pl, strides = [p.contiguous() for p in pl], {na}
+        pstride = strides.pop()
+        if iou_t.shape[1] != offs[-1]:
+            raise ValueError(f"predictions cover {offs[-1]} anchors, iou-targets {iou_t.shape[1]}")
+        lib = _C.lib()
+        need = lib.rn_iou_loss_workspace_bytes(B, offs[-1])
+        if getattr(self, "_ws_iou", None) is None or self._ws_iou.numel() < need:
+            self._ws_iou = torch.empty((need,), dtype=torch.uint8, device=dev)
+        out = torch.empty((2,), dtype=torch.float32, device=dev)
+        tail = (_C.i64_array(offs), len(levels), B, _C.ptr(iou_t), _C.ptr(normalizer), _C.ptr(weighted),
+                self._auxillary_loss_weight, grad_scale, _C.ptr(out), _C.ptr(self._ws_iou), self._ws_iou.numel(),
+                _C.current_stream())
+        with torch.cuda.device(dev):
+            if grads_bf16 is not None:
+                gi = [grads_bf16["iou-predictions"][lv] for lv in levels]
+                for p, t in zip(pl, gi):
+                    if (t.dtype not in (torch.bfloat16, torch.float16) or t.dtype != gi[0].dtype or not t.is_contiguous()
+                            or t.shape[:-1] != p.shape[:-1] or t.shape[-1] != gi[0].shape[-1] or t.shape[-1] < na):
+                        raise ValueError("grads_bf16 tensors must be contiguous 16-bit [B,H,W,stride] like the predictions")
+                lib = _C.lib(gi[0].dtype == torch.float16)   # the build whose 16-bit type the gradient tensors hold
+                _C.check(lib.rn_iou_loss_fwd_bwd_bf16(_C.ptr_array(pl), pstride, _C.ptr_array(gi), gi[0].shape[-1], na,
+                                                      *tail),
+                         "rn_iou_loss_fwd_bwd_bf16")
+            else:
+                dl = [torch.empty(p.shape, dtype=torch.float32, device=dev) for p in pl] if compute_grads else None
+                _C.check(lib.rn_iou_loss_fwd_bwd(_C.ptr_array(pl), pstride, na, _C.ptr_array(dl) if dl else None, *tail),
+                         "rn_iou_loss_fwd_bwd")
+                if compute_grads:
+                    self.grads["iou-predictions"] = dict(zip(levels, dl))
+        return out

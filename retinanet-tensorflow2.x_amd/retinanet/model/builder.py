@@ -24,7 +24,7 @@ from retinanet.dataloader.anchor_generator import AnchorBoxGenerator
 from retinanet.losses import RetinaNetLoss
 from retinanet.model.engine import InferenceEngine
 from retinanet.model.forward import half_activations
-from retinanet.model.graph import build_retinanet_graph, init_variables
+from retinanet.model.graph import build_retinanet_graph, init_variables, prune_auxillary_head
 from retinanet.model.layers import DetectionPostProcess
 
 
@@ -77,11 +77,12 @@ class RetinaNetModel:
     def layers(self):
         """Layers at the granularity the reference's executor sees after flattening one level: every ResNet conv /
         BatchNorm layer on its own (the backbone is a nested functional model), every top-level EfficientNet
-        sub-layer (stem, blocks_i), and the custom layers `fpn`, `box-head`, `class-head` as ONE layer each."""
+        sub-layer (stem, blocks_i), and the custom layers `fpn`, `box-head`, `class-head`, `auxillary-head` as ONE layer
+        each."""
         groups = OrderedDict()
         for k in self.variables:
             parts = k.split("/")
-            if parts[0] in ("fpn", "box-head", "class-head"):
+            if parts[0] in ("fpn", "box-head", "class-head", "auxillary-head"):
                 key = parts[0]
             elif parts[0].startswith("efficientnet"):
                 key = "/".join(parts[:2])
@@ -170,10 +171,14 @@ class RetinaNetModel:
             with torch.cuda.device(self.device):
                 eng.load_variables(self.variables)
 
-    def inference_engine(self, batch_size, capture_graph=False):
-        key = (int(batch_size), bool(capture_graph))
+    def inference_engine(self, batch_size, capture_graph=False, serving=False):
+        """serving=True: the engine behind `serving_default` / export — without the auxiliary IoU head, whose output
+        the post-processing stage never reads (model/builder.py:153-185); the same engine when the model has none."""
+        serving = bool(serving) and "iou-predictions" in self.graph.outputs
+        key = (int(batch_size), bool(capture_graph)) + (("serving",) if serving else ())
         if key not in self._engines:
-            self._engines[key] = InferenceEngine(self.graph, self.variables, batch_size, self.device,
+            graph = prune_auxillary_head(self.graph) if serving else self.graph
+            self._engines[key] = InferenceEngine(graph, self.variables, batch_size, self.device,
                                                  bn_epsilon=self.params.architecture.batch_norm.epsilon,
                                                  capture_graph=capture_graph,
                                                  f16=half_activations(self.params),
@@ -193,7 +198,8 @@ class RetinaNetModel:
 
     def __call__(self, images, training=False):
         """model/builder.py:94-106: images f32[B,H,W,3] -> {'class-predictions': {'3'..'7': f32[B,s,s,A*K]},
-        'box-predictions': {'3'..'7': f32[B,s,s,4A]}}.  training=True runs the training forward (batch-statistics
+        'box-predictions': {'3'..'7': f32[B,s,s,4A]}} (+ 'iou-predictions': {'3'..'7': f32[B,s,s,A]} with
+        architecture.auxillary_head.use_auxillary_head).  training=True runs the training forward (batch-statistics
         BatchNorm on the live layers, frozen layers in inference mode — executor.py:154-176) and leaves the saved
         activations in the engine for `backward`."""
         if training:
@@ -277,7 +283,7 @@ class ModelBuilder:
 
         def inference_model(images, training=False):
             if not capture_graph:
-                eng = model.inference_engine(images.shape[0])
+                eng = model.inference_engine(images.shape[0], serving=True)
                 return post(eng(images))
             # `serving_default` as ONE graph launch: the engine's launch list AND the post-processing stage's launches
             # (decode, compaction, per-class NMS, merge) are captured together — at batch 1 the step is ~75 short
@@ -287,7 +293,7 @@ class ModelBuilder:
             B = int(images.shape[0])
             st = graphs.get(B)
             if st is None:
-                eng = model.inference_engine(B)
+                eng = model.inference_engine(B, serving=True)
                 if tuple(images.shape) != tuple(eng.t["images"].shape):
                     raise ValueError(f"expected images of shape {tuple(eng.t['images'].shape)}, got {tuple(images.shape)}")
                 post_b = DetectionPostProcess(params, anchors=anchors)

@@ -17,8 +17,8 @@ import torch
 
 from retinanet import _C
 from .bottleneck import Bottleneck64, fused_blocks
-from .forward import (FoldedConvs, FusionState, conv_launch_name, conv_problem, dw_problem, fold_bn, maxpool_step, split_by_depth, stem_input,
-                      stem_pool_partner, stem_pool_step, stem_problem, tensor_readers, topdown_step)
+from .forward import (FoldedConvs, FusionState, conv_launch_name, conv_problem, dw_problem, fold_bn, maxpool_step, output_view,
+                      padded_outputs, split_by_depth, stem_input, stem_pool_partner, stem_pool_step, stem_problem, tensor_readers, topdown_step)
 from .forward import pixel_pair_kernel, pixel_pair_ok  # noqa: F401  (host-side helpers, importable from here as before)
 
 
@@ -76,9 +76,10 @@ class InferenceEngine:
         blocks = fused_blocks(self.lib, self.g, self.B, lambda blk: True)
         self._bneck_skip = {o["out"] for blk in blocks for o in blk["ops"]}     # outputs of fused ops
         inner = self._bneck_skip - {blk["name"] for blk in blocks}
+        padded = padded_outputs(self.g)
         for name, (H, W, C, dt) in self.g.tensors.items():
             if name not in inner:
-                self.t[name] = torch.empty((self.B, H, W, C), dtype=self._DT[dt], device=self.dev)
+                self.t[name] = torch.empty((self.B, H, W, padded.get(name, C)), dtype=self._DT[dt], device=self.dev)
         self.bneck = {blk["ops"][0]["out"]: Bottleneck64(self.lib, self.g, blk, self.B, self.dev, self.launch_opts,
                                                          self.t[blk["x"]], self.t[blk["name"]]) for blk in blocks}
         stem = next(o for o in self.g.ops if o["op"] == "stem")
@@ -278,7 +279,8 @@ class InferenceEngine:
                 self.step_io["balance_features"] = (set(op["tensors"]), set(op["tensors"]))
             else:
                 raise ValueError(kind)
-        self.outputs = {k: {lv: self.t[n] for lv, n in d.items()} for k, d in self.g.outputs.items()}
+        self.outputs = {k: {lv: output_view(self.t[n], self.g.tensors[n][2]) for lv, n in d.items()}
+                        for k, d in self.g.outputs.items()}
 
     # ---- run -----------------------------------------------------------------------------------
     def _launch_all(self):

@@ -13,6 +13,25 @@ import torch
 from retinanet import _C
 
 
+def padded_outputs(g):
+    """{network output tensor: channels its buffer holds}: the conv kernels write f32 outputs four channels at a time
+    (rn_conv2d_nhwc_fwd: Cout % 4 == 0), so a prediction map whose channel count is no multiple of 4 — the auxiliary
+    head's num_anchors = 9 — lives in a buffer padded to the next one.  The packed weights and the bias carry zeros in
+    the pad rows, the engines hand out the live channels as a view (`output_view`)."""
+    out = {}
+    for d in g.outputs.values():
+        for name in d.values():
+            C = g.tensors[name][2]
+            if g.tensors[name][3] == "f32" and C % 4:
+                out[name] = -(-C // 4) * 4
+    return out
+
+
+def output_view(t, C):
+    """the first C channels of output buffer `t` (the buffer itself when it holds no pad channels)"""
+    return t if t.shape[3] == C else t[..., :C]
+
+
 def split_by_depth(g, ops):
     """A grouped forward launch whose segments differ in K depth by 2x or more (the FPN lateral 1x1 convs: 512 / 1024 /
     2048 input channels) as two launches, the deep segments first.  The persistent kernels hand every XCD a contiguous range
@@ -82,7 +101,8 @@ def w_pair_ok(lib, g, cname, B, opts):
         return False
     tn = g.tensors
     shapes = [tn[o["inp"]][:2] + (tn[o["inp"]][2],) + tn[o["out"]][:2] for o in ops]
-    return _C.pair_form_kernel(lib, B, c["k"], c["stride"], ops[0]["pad"], c["cin"], c["cout"], shapes, opts) > 0
+    cout = -(-c["cout"] // 4) * 4     # the channels the launch writes (padded_outputs)
+    return _C.pair_form_kernel(lib, B, c["k"], c["stride"], ops[0]["pad"], c["cin"], cout, shapes, opts) > 0
 
 
 def stem_pool_partner(g, stem_op, readers):
@@ -220,7 +240,10 @@ class FoldedConvs:
         else:
             buf = self.buffer(cname, (lib.rn_conv_cout_pad(cout), k, k, cinp))
             _C.check(lib.rn_pack_conv_weight(_C.ptr(w), k, k, cin, cout, cinp, _C.ptr(buf), st), "rn_pack_conv_weight")
-        self.refold(op["out"], fold_bn(variables, op.get("bn"), variables.get(cname + "/bias"), self.eps, self.dev, repeat))
+        fold = fold_bn(variables, op.get("bn"), variables.get(cname + "/bias"), self.eps, self.dev, repeat)
+        if fold[2] is not None and op.get("out_dtype") == "f32" and fold[2].numel() % 4:   # padded_outputs: zero bias there
+            fold = fold[:2] + (torch.nn.functional.pad(fold[2], (0, -fold[2].numel() % 4)),)
+        self.refold(op["out"], fold)
 
     def fill(self, seg, op, t):
         """weights and inference-form epilogue of the segment of conv `op`: folded scale / shift / bias, residual"""
@@ -258,7 +281,7 @@ def conv_problem(g, ops, B, opts, splitk_ws, x_of, y_of, pair, act=None):
         s = p.seg[i]
         s.x, s.y = x.data_ptr(), y.data_ptr()
         s.N, s.H, s.W, s.Cin, s.pix_stride = B, x.shape[1], x.shape[2], c["cin"], x.shape[3]
-        s.Ho, s.Wo, s.Cout = y.shape[1], y.shape[2], c["cout"]
+        s.Ho, s.Wo, s.Cout = y.shape[1], y.shape[2], y.shape[3]   # (= c["cout"], or padded_outputs' count)
         if pair(op):
             s.W, s.Wo, s.Cin, s.Cout, s.pix_stride = x.shape[2] // 2, y.shape[2] // 2, 2 * c["cin"], 2 * c["cout"], 2 * x.shape[3]
     return p

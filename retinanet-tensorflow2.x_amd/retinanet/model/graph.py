@@ -142,13 +142,11 @@ def build_retinanet_graph(params, sync_bn_names=False):
     """The whole detector as one static graph, composed from the sub-builders exactly as the reference's
     ModelBuilder.__call__ composes its Keras layers (model/builder.py:36-106)."""
     from retinanet.model.backbone import build_backbone
-    from retinanet.model.head import build_detection_heads
+    from retinanet.model.head import build_auxillary_head, build_detection_heads
     from retinanet.model.layers.balance_features import BalanceFeatures
     from retinanet.model.neck import build_neck
     from retinanet.model.utils import get_activation_op
     arch = params.architecture
-    if arch.auxillary_head.use_auxillary_head:
-        raise NotImplementedError("auxillary head is disabled in every shipped config")
     norm = dict(arch.batch_norm)
     norm["sync_names"] = bool(sync_bn_names)
     input_shape = list(params.input.input_shape) + [int(params.input.get("channels", 3))]
@@ -169,9 +167,41 @@ def build_retinanet_graph(params, sync_bn_names=False):
     g = images.graph
     g.outputs = {"class-predictions": {lv: t.name for lv, t in class_outputs.items()},
                  "box-predictions": {lv: t.name for lv, t in box_outputs.items()}}
+    aux = arch.auxillary_head
+    if aux.use_auxillary_head:   # model/builder.py:70-101: a third head on the same features, after both others
+        auxillary_head = build_auxillary_head(
+            num_convs=aux.num_convs, filters=aux.filters, num_anchors=arch.head.num_anchors,
+            min_level=arch.feature_fusion.min_level, max_level=arch.feature_fusion.max_level,
+            conv_2d_op_params=arch.conv_2d, normalization_op_params=norm, activation_fn=activation_fn)
+        g.outputs["iou-predictions"] = {lv: t.name for lv, t in auxillary_head(features).items()}
     g.levels = list(range(int(arch.feature_fusion.min_level), int(arch.feature_fusion.max_level) + 1))
     g.meta = dict(num_anchors=int(arch.head.num_anchors), num_classes=int(arch.head.num_classes),
                   filters=int(arch.feature_fusion.filters))
+    return g
+
+
+AUXILLARY_HEAD = "auxillary-head"
+
+
+def prune_auxillary_head(graph):
+    """The graph without the auxiliary IoU head: what `serving_default` and the export path run.  The reference's
+    add_post_processing_stage reads the class and box predictions only (model/builder.py:153-185), so the saved
+    function never executes the third head.  Ops, tensors, layers and outputs of the head are dropped; everything
+    else is shared with `graph`, in the same order, so the launches are those of the same model built without the head."""
+    if "iou-predictions" not in graph.outputs:
+        return graph
+    own = lambda name: name.startswith(AUXILLARY_HEAD)
+    g = Graph()
+    g.tensors = OrderedDict((k, v) for k, v in graph.tensors.items() if not own(k))
+    g.ops = [o for o in graph.ops if not own(o.get("out", ""))]
+    g.var_specs = OrderedDict((k, v) for k, v in graph.var_specs.items() if not own(k))
+    g.convs = OrderedDict((k, v) for k, v in graph.convs.items() if not own(k))
+    g.bns = OrderedDict((k, v) for k, v in graph.bns.items() if not own(k))
+    for attr in ("dws", "ses"):
+        if hasattr(graph, attr):
+            setattr(g, attr, OrderedDict((k, v) for k, v in getattr(graph, attr).items() if not own(k)))
+    g.outputs = {k: v for k, v in graph.outputs.items() if k != "iou-predictions"}
+    g.levels, g.meta = graph.levels, graph.meta
     return g
 
 

@@ -1,6 +1,6 @@
 """`build_detection_heads(params, min_level, max_level, ...)` — retinanet/model/head/builder.py:7-43: the box head
 (4 * num_anchors outputs, zero prediction bias) and the class head (num_anchors * num_classes outputs, prediction
-bias -log((1 - 0.01) / 0.01))."""
+bias -log((1 - 0.01) / 0.01)); `build_auxillary_head` — :46-72: the IoU-prediction head."""
 from __future__ import annotations
 
 import numpy as np
@@ -28,6 +28,12 @@ def build_detection_heads(params, min_level, max_level, conv_2d_op_params=None, 
 
 def build_auxillary_head(num_convs, filters, num_anchors, min_level, max_level, conv_2d_op_params=None,
                          normalization_op_params=None, activation_fn=None):
-    """head/builder.py:46-72.  `use_auxillary_head` is false in every shipped config: the loss has no
-    iou-prediction term to train it with (retinanet_loss.py:66-83 reports 0), so the graph does not build it."""
-    raise NotImplementedError("auxillary head is disabled in every shipped config")
+    """head/builder.py:46-72: the IoU-prediction head, a third DetectionHead named `auxillary-head` with its own depth
+    and width, one output per anchor and the prediction bias -log((1 - 0.5) / 0.5) = 0."""
+    if activation_fn is None:
+        raise ValueError("`activation_fn` cannot be None")
+    prior_prob_init = -float(np.log((1 - 0.5) / 0.5))
+    return DetectionHead(num_convs=num_convs, filters=filters, output_filters=num_anchors, min_level=min_level,
+                         max_level=max_level, prediction_bias_initializer=prior_prob_init,
+                         conv_2d_op_params=conv_2d_op_params, normalization_op_params=normalization_op_params,
+                         activation_fn=activation_fn, name="auxillary-head")

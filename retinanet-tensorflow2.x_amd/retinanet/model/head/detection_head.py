@@ -25,7 +25,9 @@ class DetectionHead:
         head, act, sep = self.name, self.activation_fn, self.separable
         bn_tag = "sync_batch_normalization" if self._sync_names else "batch_normalization"
         levels = list(range(self.min_level, self.max_level + 1))
-        key = {"box-head": "box", "class-head": "class"}.get(head, head)
+        key = {"box-head": "box", "class-head": "class", "auxillary-head": "iou"}.get(head, head)
+        # the box and class heads share `tower{i}`; the auxiliary head has its own depth and width, so its own groups
+        tower = "aux_tower" if head == "auxillary-head" else "tower"
         for i in range(self.num_convs):
             for level in levels:
                 g.add_bn_layer(f"{head}/{head}-{i}-p{level}-{bn_tag}", self.filters)
@@ -35,7 +37,7 @@ class DetectionHead:
             for j, level in enumerate(levels):
                 src = features[str(level)].name if i == 0 else f"{head}_t{i - 1}_p{level}"
                 _conv_or_sep(g, sep, f"{head}_t{i}_p{level}", src, name, 3, self.filters, 0.0, self.kernel_init,
-                             f"{head}/{head}-{i}-p{level}-{bn_tag}", act, f"tower{i}", define=j == 0)
+                             f"{head}/{head}-{i}-p{level}-{bn_tag}", act, f"{tower}{i}", define=j == 0)
         name = f"{head}/{head}-prediction-conv2d"
         for j, level in enumerate(levels):
             src = f"{head}_t{self.num_convs - 1}_p{level}" if self.num_convs else features[str(level)].name

@@ -34,7 +34,7 @@ import torch
 from retinanet import _C
 from .bottleneck import Bottleneck64, fused_blocks
 from .forward import (FoldedConvs, FusionState, conv_launch_name, conv_problem, dw_problem, half_activations, maxpool_step,
-                      split_by_depth, stem_input, stem_pool_partner, stem_pool_step, stem_problem, tensor_readers,
+                      output_view, padded_outputs, split_by_depth, stem_input, stem_pool_partner, stem_pool_step, stem_problem, tensor_readers,
                       topdown_step)
 
 _DT = {"bf16": torch.bfloat16, "f32": torch.float32}
@@ -318,6 +318,16 @@ class TrainEngine:
                 self.requires[op["out"]] = True
             else:
                 raise NotImplementedError(f"training through '{kind}' ops is not built")
+        # The reference's `backbone` / `resnet_initial` freeze patterns exclude fpn, box-head and class-head by name, not
+        # the auxiliary head (model/builder.py FREEZE_VARS_REGEX), so they freeze it; its loss gradient would then have
+        # to cross frozen convs into the trainable FPN, a backward form this engine does not have
+        for op in self.ops:
+            if op["op"] in ("conv", "dwconv") and op["out"].startswith("auxillary-head") and \
+                    not self._conv_trainable(op) and self.requires.get(op["inp"]):
+                raise NotImplementedError(f"auxillary-head: {self._kvar(op)} is frozen while the layers below it train "
+                                          "(the reference's `backbone` and `resnet_initial` freeze patterns match the "
+                                          "auxillary head): backward through a frozen head is not built — freeze "
+                                          "by patterns that leave `auxillary-head` trainable")
         # a conv layer is "live" when its kernel trains; mixed frozen conv / live BN is not a shipped case
         for op in self.ops:
             if op["op"] in ("conv", "stem", "dwconv") and op.get("bn") and \
@@ -548,9 +558,10 @@ class TrainEngine:
             for o in blk["ops"]))
         self._bneck_skip = {o["out"] for blk in blocks for o in blk["ops"]}
         inner = self._bneck_skip - {blk["name"] for blk in blocks}
+        padded = padded_outputs(self.g)
         for name, (H, W, C, dt) in self.tensors.items():
             if name not in inner:
-                self.t[name] = torch.empty((B, H, W, C), dtype=self._DT[dt], device=dev)
+                self.t[name] = torch.empty((B, H, W, padded.get(name, C)), dtype=self._DT[dt], device=dev)
         self.bneck = {blk["ops"][0]["out"]: Bottleneck64(self.lib, self.g, blk, B, dev, self.launch_opts, self.t[blk["x"]],
                                                          self.t[blk["name"]]) for blk in blocks}
         self.stem_k, self.stem_pad, self.Hp, self.Wp, self.stem_in = stem_input(self.tensors, self._stem_op(), B, self.h16,
@@ -979,7 +990,8 @@ class TrainEngine:
                 a = (pin, pout, len(ts), op["mid"], B, ts[0].shape[1], ts[0].shape[2], ts[0].shape[3],
                      self.bal_avg.data_ptr())
                 self.fwd_steps.append(lambda st, a=a: _C.check(lib.rn_balance_features(*a, st), "rn_balance_features"))
-        self.outputs = {k: {lv: self.t[n] for lv, n in d.items()} for k, d in self.g.outputs.items()}
+        self.outputs = {k: {lv: output_view(self.t[n], self.tensors[n][2]) for lv, n in d.items()}
+                        for k, d in self.g.outputs.items()}
         self._bn_of_tensor = {o["out"]: (grp.problem, i, o, len(grp.ops))
                               for grp in self.bn_groups.values() for i, o in enumerate(grp.ops)}
 
@@ -1126,7 +1138,7 @@ class TrainEngine:
         self._launch_names = {id(q): n for n, q in self.conv_launches}
         # (a frozen prediction conv has no dy: such an engine serves forward() only)
         self._loss_dy = {k: {lv: self.dy_of[name] for lv, name in self.g.outputs[k].items() if name in self.dy_of}
-                         for k in ("class-predictions", "box-predictions")}
+                         for k in self.g.outputs}
         if self.dgrad_packs:
             arr = (_C.DgradPack * len(self.dgrad_packs))()
             for i, (mptr, k, cin, cout, cw, buf, mode) in enumerate(self.dgrad_packs):
@@ -1243,7 +1255,10 @@ class TrainEngine:
             p = item[0]
             sig = (p.R, p.S, p.stride_h, p.stride_w, p.pad_top, p.pad_left, p.num_segments, bytes(p.opts),
                    tuple((s.N, s.H, s.W, s.Cin, s.Ho, s.Wo, s.Cout, s.dy_pix_stride, s.x_pix_stride)
-                         for s in (p.seg[k] for k in range(p.num_segments))))
+                         for s in (p.seg[k] for k in range(p.num_segments))),
+                   # the auxiliary head's layers group among themselves: the other layers' groups stay what they are
+                   # without the head, whatever width it is given
+                   any(w.startswith("auxillary-head") for w in fn.writes))
             by_sig.setdefault(sig, []).append(i)
         drop, replace = set(), {}
         for sig, idxs in by_sig.items():
@@ -1361,11 +1376,14 @@ class TrainEngine:
             p.stride_h = p.stride_w = c["stride"]
             p.pad_top = p.pad_left = cops[0]["pad"]
             p.num_segments = len(cops)
+            # rn_conv2d_nhwc_wgrad takes Cout % 4 == 0: the auxiliary head's 9-channel prediction conv runs as 12 (dy's pad
+            # channels are zero, so rows 9 - 11 of dw are) into a buffer of its own, the live rows are copied to the arena
+            cout4 = -(-c["cout"] // 4) * 4
             for i, op in enumerate(cops):
                 x, dy = self._src(op["inp"]), dy_of[op["out"]]
                 s = p.seg[i]
                 s.x, s.dy = x.data_ptr(), dy.data_ptr()
-                s.N, s.H, s.W, s.Cin, s.Ho, s.Wo, s.Cout = B, x.shape[1], x.shape[2], c["cin"], dy.shape[1], dy.shape[2], c["cout"]
+                s.N, s.H, s.W, s.Cin, s.Ho, s.Wo, s.Cout = B, x.shape[1], x.shape[2], c["cin"], dy.shape[1], dy.shape[2], cout4
                 s.dy_pix_stride = dy.shape[3]
             # Two-stream backward: a weight-gradient launch is capped to ~2/3 of the CUs (rn_launch_opts.wgrad_target_blocks).
             # Its persistent workgroups own a CU for hundreds of microseconds; when they cover the whole chip every
@@ -1378,6 +1396,10 @@ class TrainEngine:
                 self._wgrad_capped.append((p, int(p.opts.wgrad_target_blocks)))
             ws = self._wgrad_workspace([p], lambda: lib.rn_wgrad_workspace_bytes(ctypes.byref(p)))
             dw = self._pview(kvar, self.G)
+            dw_live = None
+            if cout4 != c["cout"]:
+                dw_live, dw = dw, torch.zeros((cout4 * c["k"] * c["k"] * c["cin"],), dtype=torch.float32, device=self.dev)
+                self._keep.append(dw)
             self._keep += [p, ws]
             self.wgrad_launches.append(("wgrad:" + cname, p))
             # algorithmic FLOPs of the layer's weight gradient: 2 * pixels * k*k * Cin * Cout over the segments
@@ -1385,7 +1407,14 @@ class TrainEngine:
             step = self._wgrad_step(lib.rn_conv2d_nhwc_wgrad, (ctypes.byref(p), dw.data_ptr(), 0.0, ws.data_ptr(), ws.numel()),
                                     "rn_conv2d_nhwc_wgrad", flw, self._wgrad_bytes(p),
                                     self._wgrad_kernel_name(p) + " + wgrad_reduce_kernel", "wgrad:" + cname, [kvar])
-            step.wgrad_item = (p, dw, ws, flw)      # _group_wgrad_steps may merge it with same-shape layers
+            if dw_live is None:
+                step.wgrad_item = (p, dw, ws, flw)      # _group_wgrad_steps may merge it with same-shape layers
+            else:
+                def padded_wgrad(st, step=step, src=dw, dst=dw_live):
+                    step(st)
+                    _C.check(lib.rn_reduce_rows_f32(_C.ptr(src), 1, dst.numel(), dst.numel(), 0.0, _C.ptr(dst), st),
+                             "live rows of a padded weight gradient")
+                step = self._side(padded_wgrad, writes=[kvar])
             self.bwd_steps.append(step)
             if c["bias"]:
                 # bias gradient = column sums of dy over every segment (two-stage reduction kernel)
@@ -1729,8 +1758,8 @@ class TrainEngine:
         -> parameter gradients in self.G."""
         lib, st = self.lib, _C.current_stream()
         if loss_grads is not None:   # None: the loss kernels already wrote bf16 into loss_grad_buffers()
-            for key, okey in (("class-predictions", "class-predictions"), ("box-predictions", "box-predictions")):
-                for lv, name in self.g.outputs[okey].items():
+            for key in self.g.outputs:   # class-predictions, box-predictions (+ iou-predictions: the auxiliary head)
+                for lv, name in self.g.outputs[key].items():
                     gsrc = loss_grads[key][lv]
                     dst = self.dy_of[name]
                     C = gsrc.shape[-1]
