@@ -149,7 +149,7 @@ def maybe_enable_native(engine):
     logging.info("SyncBN / normaliser messages go through rn_comm (RCCL on the compute stream)")
     # C1: a second communicator for the gradient buckets (one communicator per stream that carries collectives): with it
     # a bucket's all-reduce is ONE rn_allreduce_bucket enqueued on the stream that prepared the bucket, in program order —
-    # no c10d stream, no event hop (TrainEngine._launch_bucket).  Its construction is collective like the first one's; a
+    # no c10d stream, no event hop (GradientOverlap._launch_bucket).  Its construction is collective like the first one's; a
     # failure anywhere leaves the buckets on torch.distributed.
     comm2 = NativeComm(dist.get_rank(engine.pg), engine.world, engine.dev, engine.pg,
                        handle=getattr(engine, "handle", None), slot=1)

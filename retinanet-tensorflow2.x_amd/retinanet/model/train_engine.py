@@ -33,6 +33,7 @@ import torch
 
 from retinanet import _C
 from .bottleneck import Bottleneck64, fused_blocks
+from .data_parallel import GradientOverlap, SmallMessages
 from .forward import (FoldedConvs, FusionState, conv_launch_name, conv_problem, dw_problem, half_activations, maxpool_step,
                       output_view, padded_outputs, split_by_depth, stem_input, stem_pool_partner, stem_pool_step, stem_problem, tensor_readers,
                       topdown_step)
@@ -60,6 +61,20 @@ class BnGroup(NamedTuple):
     ops: list
 
 
+class BackwardStep:
+    """One entry of TrainEngine.bwd_steps.  run(stream) enqueues it; side: only the optimizer reads its results (weight /
+    bias gradients), so the two-stream backward runs it on the weight-gradient stream; writes: the variables whose
+    gradient it completes (bucket readiness of the overlapped all-reduce); wgrad: (problem, dw, workspace, FLOPs) of a
+    weight-gradient launch that _group_wgrad_steps may merge with same-shape layers."""
+    __slots__ = ("run", "side", "writes", "wgrad")
+
+    def __init__(self, run, side=False, writes=(), wgrad=None):
+        self.run, self.side, self.writes, self.wgrad = run, side, writes, wgrad
+
+    def __call__(self, st):
+        return self.run(st)
+
+
 class TrainEngine:
     def __init__(self, model, batch_size, frozen_regexes=(), process_group=None, world_size=None, frozen_names=(),
                  launch_opts=None, wide_pred_terms=None, force_dp=None):
@@ -85,8 +100,8 @@ class TrainEngine:
         self.params_cfg = model.params
         self.B = int(batch_size)
         self.dev = model.device
-        # ---- switches: every environment read of the engine, once.  (RNET_C1_OVERLAP alone is read at the head of every
-        # backward pass, _overlap_begin: bench.py and the data-parallel tests flip it on a live engine.)
+        # ---- switches: every environment read of the engine, once.  (GradientOverlap reads its own; RNET_C1_OVERLAP at the head
+        # of every backward pass: bench.py and the data-parallel tests flip it on a live engine.)
         env = os.environ.get
         if force_dp is None:
             force_dp = env("RNET_FORCE_DP", "0") == "1"
@@ -113,8 +128,6 @@ class TrainEngine:
             self._wgrad_cap = (self._wgrad_cap[0], 2 * self._wgrad_cap[0])
         self._wgrad_group_mode = env("RNET_WGRAD_GROUP", "halo")   # "0" | "halo" | "all": see _group_wgrad_steps
         self._ab_workspaces = env("RNET_AB_WORKSPACES") == "1"     # tools/ab_step.py switches kernel families between rounds
-        self._stream_probe = env("RNET_STREAM_PROBE", "1") != "0"  # _bucket_group_is_safe
-        self._bucket_bytes = int(env("RNET_C1_BUCKET_MB", "25")) << 20
         # ---- configuration
         self.f16 = half_activations(model.params)    # (+ the LossScaleOptimizer arithmetic of optimizer_step)
         self.h16 = torch.float16 if self.f16 else torch.bfloat16
@@ -186,28 +199,10 @@ class TrainEngine:
         # kernel) for EVERY implicit-GEMM launch of the step — forward, data gradient, weight gradient
         self.layer_profile = None
         self.hbm_profile = None   # bench.py: list that collects (event0, event1, kernel name, algorithmic bytes)
-        # ---- data parallel
-        self._c2_local, self._c2_sent, self.c2_normalizer = None, False, None
-        self.native_comm = None   # retinanet.comm.NativeComm for the small per-layer messages (SyncBN, normaliser)
-        self.native_comm_buckets = None   # ... and a second one for the gradient buckets (rn_allreduce_bucket), or None
-        self._small_msgs = 0      # C3 messages (SyncBN sums; C2 rides in the first) sent since the step began
+        # ---- data parallel (self.overlap follows the arenas it works on)
+        self.small = SmallMessages(self.lib, self.dev, self.pg, self.world, self.sync_bn)
         self.syncbn_messages_per_step = None   # their count in the last train_step (bench.py: config.syncbn_messages)
-        self._overlap_on = False
-        self._overlap_done = 0
-        self._overlap_works = []
-        self._buckets = None      # the gradient buckets of the overlapped all-reduce, planned by the first pass that uses them
-        self._bucket_at = {}      # backward step -> buckets complete after it
-        self._comm_events = []    # per bucket: "the main stream's gradients of this bucket are enqueued"
-        self._bucket_stream = None   # the stream that carried the last pass's buckets
-        self._overlap_last_event = None   # recorded behind the last bucket launched
-        self.L = None             # what this rank contributed to the buckets (for the clip correction)
-        self.pg_c1 = None         # the buckets' own process group
-        self._probe_bucket_group = False   # pg_c1 is new: _bucket_group_is_safe has not looked at it yet
-        self._overlap_unsafe = False       # ... and found that its stream blocks the main stream: plain order
-        self._flag_host = self._flag_event = None   # pinned copy of the clip flag G[0] and its event
-        self.clip_fired = False
-        self.bucket_host_ms = 0.0
-        self.price_without_flag_read = False   # bench.py's extra.dp_overhead sets it: see _overlap_finish
+        self.price_without_flag_read = False   # bench.py's extra.dp_overhead sets it: see GradientOverlap.finish
         self._prepare_graph()
         with torch.cuda.device(self.dev):
             # split-K of the persistent conv kernels' last round (rn_conv_problem.splitk_ws): every forward / data-gradient
@@ -226,6 +221,12 @@ class TrainEngine:
             self._build_forward()
             self._build_backward()
             self._group_wgrad_steps()
+            self.overlap = GradientOverlap(
+                self.lib, self.dev, G=self.G, P=self.P, metrics=self.metrics, segs_dev=self.segs_dev,
+                block_seg_dev=self.block_seg_dev, n_blocks=self.n_blocks, n_segs=self.n_segs, opt_ws=self.opt_ws,
+                train_names=self.train_names, p_off=self.p_off, seg_blocks=self._seg_blocks, ready_steps=self._ready_steps,
+                small=self.small, pg=self.pg, world=self.world, dp_active=self.dp_active,
+                side_stream=lambda: self._side_stream)
             for name, cp in self.conv_launches:   # a launch writes stage-1 BatchNorm partials for all its segments or none
                 marks = {bool(cp.seg[i].bn_bwd_y) for i in range(cp.num_segments)}
                 if name.startswith("dgrad:") and len(marks) != 1:
@@ -744,16 +745,6 @@ class TrainEngine:
         self._keep.append(p)
         return p
 
-    def _allreduce_small(self, t):
-        """SyncBatchNorm / normaliser message: rn_allreduce_small on the compute stream when a native communicator was
-        handed in (retinanet.comm.maybe_enable_native), torch.distributed otherwise"""
-        self._small_msgs += 1
-        if self.native_comm is not None:
-            self.native_comm.all_reduce_small(t)
-        else:
-            import torch.distributed as dist
-            dist.all_reduce(t, group=self.pg)
-
     def _bn_pass(self, kind, pb, fn):
         """BatchNorm elementwise / reduction passes (HBM-bound): bench.py brackets them with events on the launch stream.
         Algorithmic bytes: apply = read y + write z (+ residual); bwd_reduce = read y + dz (+ z for the residual
@@ -781,15 +772,8 @@ class TrainEngine:
         if not self.sync_bn:
             _C.check(lib.rn_bn_stats_finalize(prb, _C.ptr(ws), ws.numel(), st), "rn_bn_stats_finalize")
             return
-        from retinanet.distribute import syncbn_merge
         _C.check(lib.rn_bn_stats(prb, _C.ptr(ws), ws.numel(), st), "rn_bn_stats")
-        # C2 (the loss normaliser's scalar all-reduce, retinanet_loss.py:46-49) rides in the spare slot of the step's
-        # FIRST SyncBN message instead of being a collective of its own
-        fold = self._c2_local is not None and not self._c2_sent
-        norm = syncbn_merge(sums, self.world, self._allreduce_small, self._c2_local if fold else None)
-        if fold:
-            self._c2_sent = True
-            self.c2_normalizer = norm
+        self.small.merge_stats(sums)
         _C.check(lib.rn_bn_finalize(prb, st), "rn_bn_finalize")
 
     def _bn_problem(self, ops, conv_problem=None):
@@ -1054,9 +1038,9 @@ class TrainEngine:
                      self._pview(name + "/conv2d_1/kernel", self.G).data_ptr(),
                      self._pview(name + "/conv2d_1/bias", self.G).data_ptr(), self.se_ws.data_ptr(), self.se_ws.numel())
                 self.se_launches.append(("se:" + op["out"], "bwd", B, x.shape[1] * x.shape[2], se["C"], se["se"]))
-                se_bwd = lambda st, a=a: _C.check(lib.rn_squeeze_excite_bwd(*a, st), "rn_squeeze_excite_bwd")
-                se_bwd.writes = [name + sfx for sfx in ("/conv2d/kernel", "/conv2d/bias", "/conv2d_1/kernel", "/conv2d_1/bias")]
-                self.bwd_steps.append(se_bwd)
+                self.bwd_steps.append(BackwardStep(
+                    lambda st, a=a: _C.check(lib.rn_squeeze_excite_bwd(*a, st), "rn_squeeze_excite_bwd"),
+                    writes=[name + sfx for sfx in ("/conv2d/kernel", "/conv2d/bias", "/conv2d_1/kernel", "/conv2d_1/bias")]))
             elif kind == "maxpool":
                 op = item
                 if not self.requires.get(op["inp"]):
@@ -1065,7 +1049,7 @@ class TrainEngine:
                 acc = 0 if mark(op["inp"]) else 1
                 a = (x.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, x.shape[1], x.shape[2], x.shape[3], op["k"],
                      op["stride"], op["pad_top"], op["pad_left"], dy.shape[1], dy.shape[2], acc)
-                self.bwd_steps.append(lambda st, a=a: _C.check(lib.rn_maxpool2d_nhwc_bwd(*a, st), "maxpool_bwd"))
+                self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_maxpool2d_nhwc_bwd(*a, st), "maxpool_bwd")))
             elif kind == "stem":
                 op = item
                 if not self._conv_trainable(op):
@@ -1089,13 +1073,12 @@ class TrainEngine:
                 self._keep += [pw, wsw, dwp]
                 bn_bwd = self._bn_bwd_step(grp, grp.ws, profiled=False)   # (its two passes were never rows of hbm_profile)
 
-                def stem_bwd(st, bn_bwd=bn_bwd, pw=pw, wsw=wsw, dwp=dwp, gview=gview, k=k):
+                def stem_bwd(st, bn_bwd=bn_bwd.run, pw=pw, wsw=wsw, dwp=dwp, gview=gview, k=k):
                     bn_bwd(st)
                     _C.check(lib.rn_conv2d_nhwc_wgrad(ctypes.byref(pw), dwp.data_ptr(), 0.0, wsw.data_ptr(),
                                                       wsw.numel(), st), "stem wgrad")
                     gview.copy_(dwp[:, :, :k, :3])   # [co][r][8 taps x 4 ch] -> [co][r][s][c]
-                stem_bwd.writes = [self._kvar(op)] + bn_bwd.writes
-                self.bwd_steps.append(stem_bwd)
+                self.bwd_steps.append(BackwardStep(stem_bwd, writes=[self._kvar(op)] + bn_bwd.writes))
             elif kind == "topdown":
                 op = item
                 L = len(op["ins"])
@@ -1116,7 +1099,8 @@ class TrainEngine:
                     outp = self.t[op["outs"][l]].data_ptr() if l < L - 1 else None
                     a = (dout.data_ptr(), prev, outp, din.data_ptr(), B, dout.shape[1], dout.shape[2], dout.shape[3],
                          act if l < L - 1 else _C.RN_ACT_NONE)
-                    self.bwd_steps.append(lambda st, a=a: _C.check(lib.rn_fpn_topdown_bwd_level(*a, st), "topdown_bwd"))
+                    self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_fpn_topdown_bwd_level(*a, st),
+                                                                                "topdown_bwd")))
                     prev = din.data_ptr()
             elif kind == "balance":
                 op = item
@@ -1133,7 +1117,7 @@ class TrainEngine:
                 self._keep += [pd, pi, pn, scratch]
                 a = (pd, pi, pn, self.bal_avg.data_ptr(), scratch.data_ptr(), scratch.numel(), len(names), op["mid"], B,
                      ins[0].shape[1], ins[0].shape[2], ins[0].shape[3])
-                self.bwd_steps.append(lambda st, a=a: _C.check(lib.rn_balance_features_bwd(*a, st), "balance_bwd"))
+                self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_balance_features_bwd(*a, st), "balance_bwd")))
         # what the steps look up, static from here on
         self._launch_names = {id(q): n for n, q in self.conv_launches}
         # (a frozen prediction conv has no dy: such an engine serves forward() only)
@@ -1162,7 +1146,8 @@ class TrainEngine:
             if l == L - 1:
                 a = (dout.data_ptr(), prev_g, prev_coef, None, None, None, None, None, din.data_ptr(), None, 0, B, H, W, C,
                      _C.RN_ACT_NONE)
-                self.bwd_steps.append(lambda st, a=a: _C.check(lib.rn_fpn_fused_bwd_level(*a, st), "fused_topdown_bwd"))
+                self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_fpn_fused_bwd_level(*a, st),
+                                                                            "fused_topdown_bwd")))
                 break
             ws = torch.empty((lib.rn_fpn_fused_bwd_workspace_bytes(B, H, W, C),), dtype=torch.uint8, device=self.dev)
             coef = fus.coef[l].data_ptr()
@@ -1181,8 +1166,7 @@ class TrainEngine:
                 _C.check(lib.rn_fpn_fused_bwd_level(*a, st), "fused_topdown_bwd")
                 if finalize:
                     _C.check(lib.rn_fpn_fused_bwd_finalize(*f, st), "fused_topdown_bwd_finalize")
-            level.writes = live
-            self.bwd_steps.append(level)
+            self.bwd_steps.append(BackwardStep(level, writes=live))
             prev_g, prev_coef = dout.data_ptr(), coef
 
     def set_wgrad_cap(self, on):
@@ -1225,7 +1209,7 @@ class TrainEngine:
             nws = max(nws, largest("wgrad_kernel", (1, 3)))
         return torch.empty((max(nws, 256),), dtype=torch.uint8, device=self.dev)
 
-    def _wgrad_step(self, call, args, what, flops, byts, kname, lname, writes):
+    def _wgrad_step(self, call, args, what, flops, byts, kname, lname, writes, item=None):
         """Side-stream step of one weight-gradient library call `call(*args, stream)`, bracketed with events on the stream
         it goes to (the side stream in the two-stream backward) while bench.py collects wgrad_profile / layer_profile."""
         def wgrad(st):
@@ -1234,7 +1218,7 @@ class TrainEngine:
                 _C.check(call(*args, st), what)
                 return
             self._timed(lambda: _C.check(call(*args, st), what), (prof, (flops, kname)), (lprof, (lname, flops, byts, kname)))
-        return self._side(wgrad, writes=writes)
+        return BackwardStep(wgrad, side=True, writes=writes, wgrad=item)
 
     def _group_wgrad_steps(self):
         """Weight-gradient launches of layers with IDENTICAL geometry become one rn_conv2d_nhwc_wgrad_group call (the
@@ -1248,17 +1232,16 @@ class TrainEngine:
         if self._wgrad_group_mode == "0":
             return
         by_sig = {}
-        for i, fn in enumerate(self.bwd_steps):
-            item = getattr(fn, "wgrad_item", None)
-            if item is None:
+        for i, step in enumerate(self.bwd_steps):
+            if step.wgrad is None:
                 continue
-            p = item[0]
+            p = step.wgrad[0]
             sig = (p.R, p.S, p.stride_h, p.stride_w, p.pad_top, p.pad_left, p.num_segments, bytes(p.opts),
                    tuple((s.N, s.H, s.W, s.Cin, s.Ho, s.Wo, s.Cout, s.dy_pix_stride, s.x_pix_stride)
                          for s in (p.seg[k] for k in range(p.num_segments))),
                    # the auxiliary head's layers group among themselves: the other layers' groups stay what they are
                    # without the head, whatever width it is given
-                   any(w.startswith("auxillary-head") for w in fn.writes))
+                   any(w.startswith("auxillary-head") for w in step.writes))
             by_sig.setdefault(sig, []).append(i)
         drop, replace = set(), {}
         for sig, idxs in by_sig.items():
@@ -1266,7 +1249,7 @@ class TrainEngine:
                 grp = idxs[lo:lo + 8]
                 if len(grp) < 2:
                     continue
-                items = [self.bwd_steps[i].wgrad_item for i in grp]
+                items = [self.bwd_steps[i].wgrad for i in grp]
                 probs = [it[0] for it in items]
                 arr = (ctypes.POINTER(_C.WgradProblem) * len(grp))(*[ctypes.pointer(p) for p in probs])
                 if lib.rn_wgrad_group_fused(arr, len(grp)) != 1:
@@ -1293,7 +1276,7 @@ class TrainEngine:
                     wname, lname, [w for i in grp for w in self.bwd_steps[i].writes])
                 drop.update(grp[:-1])
                 self.wgrad_groups.append(probs)
-        self.bwd_steps = [replace.get(i, fn) for i, fn in enumerate(self.bwd_steps) if i not in drop]
+        self.bwd_steps = [replace.get(i, step) for i, step in enumerate(self.bwd_steps) if i not in drop]
 
     def _bn_bwd_step(self, grp, ws, profiled=True):
         """BatchNorm backward of the layers of BnGroup `grp`: reduction (over the partials in `ws`) -> SyncBN all-reduce
@@ -1305,10 +1288,9 @@ class TrainEngine:
             bracket("bn_bwd_reduce", pb, lambda: _C.check(lib.rn_bn_bwd_reduce(prb, _C.ptr(ws), ws.numel(), st),
                                                            "rn_bn_bwd_reduce"))
             if self.sync_bn:
-                self._allreduce_small(bsums)
+                self.small.all_reduce(bsums)
             bracket("bn_bwd_apply", pb, lambda: _C.check(lib.rn_bn_bwd_apply(prb, st), "rn_bn_bwd_apply"))
-        run.writes = [op["bn"] + sfx for op in grp.ops for sfx in ("/gamma", "/beta")]
-        return run
+        return BackwardStep(run, writes=[op["bn"] + sfx for op in grp.ops for sfx in ("/gamma", "/beta")])
 
     @staticmethod
     def _distinct_inputs(ops):
@@ -1360,7 +1342,7 @@ class TrainEngine:
                     dy_of[op["out"]] = dyb
                     a = (self.grad[op["out"]].data_ptr(), self.t[op["out"]].data_ptr(), dyb.data_ptr(),
                          dyb.numel(), _C.ACT_IDS[op["act"]])
-                    self.bwd_steps.append(lambda st, a=a: _C.check(lib.rn_act_bwd(*a, st), "rn_act_bwd"))
+                    self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_act_bwd(*a, st), "rn_act_bwd")))
             self._keep += list(dy_of.values())
         self.dy_of.update(dy_of)
         # (b) weight / bias gradients, one problem per distinct (shared) conv layer
@@ -1404,17 +1386,17 @@ class TrainEngine:
             self.wgrad_launches.append(("wgrad:" + cname, p))
             # algorithmic FLOPs of the layer's weight gradient: 2 * pixels * k*k * Cin * Cout over the segments
             flw = sum(2 * B * p.seg[i].Ho * p.seg[i].Wo * c["k"] * c["k"] * c["cin"] * c["cout"] for i in range(len(cops)))
+            # (a layer with a buffer of its own stays out of _group_wgrad_steps' merge of same-shape layers)
             step = self._wgrad_step(lib.rn_conv2d_nhwc_wgrad, (ctypes.byref(p), dw.data_ptr(), 0.0, ws.data_ptr(), ws.numel()),
                                     "rn_conv2d_nhwc_wgrad", flw, self._wgrad_bytes(p),
-                                    self._wgrad_kernel_name(p) + " + wgrad_reduce_kernel", "wgrad:" + cname, [kvar])
-            if dw_live is None:
-                step.wgrad_item = (p, dw, ws, flw)      # _group_wgrad_steps may merge it with same-shape layers
-            else:
-                def padded_wgrad(st, step=step, src=dw, dst=dw_live):
-                    step(st)
+                                    self._wgrad_kernel_name(p) + " + wgrad_reduce_kernel", "wgrad:" + cname, [kvar],
+                                    item=(p, dw, ws, flw) if dw_live is None else None)
+            if dw_live is not None:
+                def padded_wgrad(st, wgrad=step.run, src=dw, dst=dw_live):
+                    wgrad(st)
                     _C.check(lib.rn_reduce_rows_f32(_C.ptr(src), 1, dst.numel(), dst.numel(), 0.0, _C.ptr(dst), st),
                              "live rows of a padded weight gradient")
-                step = self._side(padded_wgrad, writes=[kvar])
+                step = BackwardStep(padded_wgrad, side=True, writes=step.writes)
             self.bwd_steps.append(step)
             if c["bias"]:
                 # bias gradient = column sums of dy over every segment (two-stage reduction kernel)
@@ -1452,7 +1434,7 @@ class TrainEngine:
                     _C.check(lib.rn_bn_stats(pr, _C.ptr(ws2), ws2.numel(), st), "bias colsum")
                     # sum of the per-level column sums (row 0 of every [2][cw] block), levels in order
                     _C.check(lib.rn_reduce_rows_f32(_C.ptr(bs), rows, stride, n, 0.0, _C.ptr(db), st), "bias grad")
-                self.bwd_steps.append(self._side(bias_grad, writes=[cname + "/bias"]))
+                self.bwd_steps.append(BackwardStep(bias_grad, side=True, writes=[cname + "/bias"]))
         # (c) data gradients
         packs = {}
         for sub in self._distinct_inputs([op for op in ops if self.requires.get(op["inp"])]):
@@ -1489,8 +1471,8 @@ class TrainEngine:
             self._keep += [p, ws]
             self.dw_wgrad_launches.append(("dw_wgrad:" + dname, p))
             a = (ctypes.byref(p), self._pview(d["kvar"], self.G).data_ptr(), ws.data_ptr(), ws.numel())
-            self.bwd_steps.append(self._side(lambda st, a=a: _C.check(lib.rn_depthwise_conv2d_nhwc_wgrad(*a, st),
-                                                                     "dw wgrad"), writes=[d["kvar"]]))
+            self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_depthwise_conv2d_nhwc_wgrad(*a, st), "dw wgrad"),
+                                               side=True, writes=[d["kvar"]]))
         flips = {}
         for sub in self._distinct_inputs([op for op in ops if self.requires.get(op["inp"])]):
             d0 = self.g.dws[sub[0]["dw"]]
@@ -1527,7 +1509,7 @@ class TrainEngine:
                 for u in ups:
                     _C.check(lib.rn_upsample_zero2x(*u, st), "rn_upsample_zero2x")
                 _C.check(lib.rn_depthwise_conv2d_nhwc_fwd(ctypes.byref(p), st), "dw dgrad")
-            self.bwd_steps.append(dgrad)
+            self.bwd_steps.append(BackwardStep(dgrad))
 
     def _bn_bwd_fusable(self, name):
         """(rn_bn_problem, segment) of the BatchNorm + ReLU layer that produced `name` when stage 1 of its backward
@@ -1670,7 +1652,7 @@ class TrainEngine:
             self._launch_conv(p, st, "dgrad")
             for a in post:
                 _C.check(post_op[0](*a, st), post_op[1])
-        self.bwd_steps.append(dgrad)
+        self.bwd_steps.append(BackwardStep(dgrad))
 
     # ---- one training step -----------------------------------------------------------------------------
     def refresh_dgrad_weights(self, st):
@@ -1704,20 +1686,12 @@ class TrainEngine:
             fn(st)
         return self.outputs
 
-    @staticmethod
-    def _side(fn, writes=()):
-        """marks a backward step whose results only the optimizer reads (weight / bias gradients); `writes` = the
-        variables whose gradient the step completes (bucket readiness of the overlapped all-reduce)"""
-        fn.side = True
-        fn.writes = list(writes)
-        return fn
-
     def _ensure_side_stream(self):
         if self._side_stream is None:
             # a stream that really runs beside the caller's (probed: HIP's stream -> hardware-queue map depends on how
             # many streams the process created before — _C.concurrent_stream)
             probes, agree = [], None
-            if self.dp_active and self.sync_bn and self.native_comm is None:
+            if self.small.through_c10d:
                 import torch.distributed as dist
                 if dist.is_available() and dist.is_initialized() and dist.get_backend(self.pg) == "nccl":
                     # the SyncBN messages hop main -> c10d's stream -> main: that stream must not share a queue with this
@@ -1770,12 +1744,12 @@ class TrainEngine:
             self._dgrad_prepacked = False
         else:
             self.refresh_dgrad_weights(st)
-        overlap = self._overlap_begin()
+        overlap = self.overlap.begin(self._train_step_active, self._step_args)
         if not self.side_stream_on:
-            for i, fn in enumerate(self.bwd_steps):
-                fn(st)
+            for i, step in enumerate(self.bwd_steps):
+                step.run(st)
                 if overlap:
-                    self._overlap_after_step(i, torch.cuda.current_stream(self.dev), None)
+                    self.overlap.after_step(i, torch.cuda.current_stream(self.dev), None)
             return
         # two streams: a side step waits (event) for everything the main stream has enqueued so far — its inputs
         # dy / x are complete at that point and are not written again before the join below — and the main stream
@@ -1784,226 +1758,56 @@ class TrainEngine:
         side = self._ensure_side_stream()
         sst = ctypes.c_void_p(side.cuda_stream)
         fresh = False            # the side stream already waits for the newest main-stream work
-        for i, fn in enumerate(self.bwd_steps):
-            if getattr(fn, "side", False):
+        for i, step in enumerate(self.bwd_steps):
+            if step.side:
                 if not fresh:
                     ev = self._side_events[i]
                     ev.record(main)
                     side.wait_event(ev)
                     fresh = True
                 with torch.cuda.stream(side):
-                    fn(sst)
+                    step.run(sst)
             else:
-                fn(st)
+                step.run(st)
                 fresh = False
             if overlap:
-                self._overlap_after_step(i, main, side)
+                self.overlap.after_step(i, main, side)
         main.wait_stream(side)
 
-    # ---- gradient all-reduce overlapped with the backward pass -------------------------------------
-    # executor.py:432-437 clips the LOCAL gradients and then sums them over the replicas; the clip factors need every
-    # gradient, so a literal translation can only start the all-reduce after the whole backward pass.  Here the
-    # buckets go out as the backward pass completes them, UNclipped ("optimistic": local gradients are pre-divided by
-    # the replica count, so the per-tensor / global norms sit far below clipnorm after the first steps), each rank
-    # keeps a copy of what it sent, and at the end one flag that rode in the last bucket says whether any rank's
-    # factor was != 1.  Only then is the correction sum_r (factor_r - 1) * g_r all-reduced and added — the result is
-    # sum_r factor_r * g_r, the reference's clip-then-sum.
-    def _plan_buckets(self):
-        bucket_bytes = self._bucket_bytes
-        written = {}
-        for i, fn in enumerate(self.bwd_steps):
-            for k in getattr(fn, "writes", ()):
-                written[k] = i
-        missing = [k for k in self.train_names if k not in written]
+    def _ready_steps(self):
+        """variable -> index of the last backward step that writes its gradient (GradientOverlap plans its buckets by it)"""
+        ready = {k: i for i, step in enumerate(self.bwd_steps) for k in step.writes}
+        missing = [k for k in self.train_names if k not in ready]
         if missing:
             raise RuntimeError(f"no backward step completes the gradient of {missing[:4]}")
-        buckets, cur = [], None
-        for k in self.train_names:     # arena order = forward order: the backward pass completes the tail first
-            off, n = self.p_off[k]
-            b0, nb = self._seg_blocks[k]
-            if cur is None or (cur["end"] - cur["begin"]) * 4 >= bucket_bytes:
-                cur = dict(begin=off, end=off, block_begin=b0, block_count=0, ready=-1)
-                buckets.append(cur)
-            cur["end"] = (off + n + 3) // 4 * 4
-            cur["block_count"] += nb
-            cur["ready"] = max(cur["ready"], written[k])
-        buckets[0]["begin"] = 0        # the flag slots ride in the bucket that completes last
-        order = sorted(range(len(buckets)), key=lambda j: (buckets[j]["ready"], -j))
-        if order[-1] != 0:             # keep the invariant simple: bucket 0 goes last
-            buckets[0]["ready"] = max(b["ready"] for b in buckets)
-        self._buckets = buckets
-        self._bucket_at = {}
-        for j, bkt in enumerate(buckets):
-            self._bucket_at.setdefault(bkt["ready"], []).append(j)
-        for lst in self._bucket_at.values():
-            lst.sort(reverse=True)     # bucket 0 after the others that become ready with the same step
+        return ready
 
-    def _overlap_begin(self):
-        """True when this backward pass launches the gradient all-reduce bucket by bucket (world > 1, or forced
-        with RNET_C1_OVERLAP=1 for the single-replica equivalence test)."""
-        mode = os.environ.get("RNET_C1_OVERLAP", "auto")
-        on = self._train_step_active and (mode == "1" or (mode != "0" and self.dp_active))
-        self._overlap_works = []
-        self._overlap_on = on
-        if not on:
-            return False
-        if self._buckets is None:
-            self._plan_buckets()
-            # Which stream prepares a bucket and hands it to RCCL.  Round 3 used a third stream of its own; round 5 measured
-            # (tools/probes/dp_overlap_trace.py, 1-rank nccl group on one MI355X, rocprofv3 kernel trace) that HIP mapped
-            # it onto the SAME hardware queue as the weight-gradient stream: a bucket's "wait for the main stream" packet
-            # then sat in front of weight-gradient kernels that had nothing to wait for — 2.3 ms of chip idle per step
-            # against 0.7 ms, step 34.4 ms against 31.4 ms for the plain order (and 44 ms with GPU_MAX_HW_QUEUES=8) — the
-            # overlap machinery cost more than the all-reduce it hides.  So the bucket work rides on the weight-gradient
-            # stream itself (most of a bucket's producers are there; it waits for the main stream's BatchNorm gamma / beta
-            # gradients through one event per bucket) or, in the one-stream backward, on the main stream: no extra queue.
-            self._comm_events = [torch.cuda.Event() for _ in self._buckets]
-            self.L = torch.zeros_like(self.G)      # what this rank contributed (for the clip correction)
-            self._flag_host = torch.zeros((1,), dtype=torch.float32, pin_memory=True)
-            self._flag_event = torch.cuda.Event()
-            if self.dp_active:
-                import torch.distributed as dist
-                self._probe_bucket_group = True
-                # its own communicator: the latency-bound SyncBN all-reduces of the main stream must not queue
-                # behind a 25 MB bucket on the same RCCL stream
-                self.pg_c1 = dist.new_group(backend=dist.get_backend(self.pg))
-        if self._probe_bucket_group:
-            self._probe_bucket_group = False
-            if self.native_comm_buckets is None and not self._bucket_group_is_safe():
-                # c10d's stream for the bucket group shares a hardware queue with the main stream: every bucket's "wait for
-                # the weight-gradient stream" packet would stall the main stream's kernels behind it.  All ranks agreed
-                # (MIN): this job keeps the plain order — all-reduce after the backward pass.
-                import logging
-                logging.warning("gradient-bucket overlap disabled: c10d's stream for the bucket group blocks the main stream "
-                                "on this process's hardware-queue map (RNET_STREAM_PROBE=0 skips the probe)")
-                self._overlap_unsafe = True
-        if self._overlap_unsafe:
-            self._overlap_on = False
-            return False
-        self._overlap_done = 0
-        return True
+    # ---- what bench.py and retinanet.comm reach through the engine ---------------------------------------------------
+    _buckets = property(lambda self: self.overlap.buckets)
+    _overlap_unsafe = property(lambda self: self.overlap.unsafe)
+    clip_fired = property(lambda self: self.overlap.clip_fired)
+    bucket_host_ms = property(lambda self: self.overlap.bucket_host_ms)
 
-    def _bucket_group_is_safe(self):
-        """Does an async all-reduce of the bucket group, issued from the weight-gradient stream while that stream still
-        waits for something, leave the main stream alone — its kernels AND the SyncBN all-reduces it issues through the
-        other group (two c10d streams on one hardware queue: every SyncBN message would wait for the bucket's producers)?
-        (_C.wait_blocks; collective: the ranks agree.)  c10d picks a group's stream when the group is first used, so a group
-        that fails is replaced by a fresh one, three times at most."""
-        import torch.distributed as dist
-        side = self._side_stream
-        if side is None or not self._stream_probe or dist.get_backend(self.pg_c1) != "nccl":
-            return True
-        main = torch.cuda.current_stream(self.dev)
-        tiny = torch.zeros((64,), dtype=torch.float32, device=self.dev)
-        tiny2 = torch.zeros((64,), dtype=torch.float32, device=self.dev)
-        helper = torch.cuda.Stream(self.dev)
-        self._keep.append(helper)
-        for attempt in range(4):
-            with torch.cuda.stream(side):
-                dist.all_reduce(tiny, group=self.pg_c1)          # c10d picks the group's stream at its first collective
-            torch.cuda.synchronize(self.dev)
-            blocked = False
-            probes = [lambda: _C.check(self.lib.rn_probe_spin(1, ctypes.c_void_p(main.cuda_stream)), "rn_probe_spin")]
-            if self.sync_bn and self.native_comm is None:
-                probes.append(lambda: dist.all_reduce(tiny2, group=self.pg))
-            for probe in probes:                                 # (every probe on every rank: they may be collectives)
-                works = []
+    @property
+    def native_comm(self):
+        return self.small.native_comm
 
-                def pre(works=works):   # the group's stream now waits for the weight-gradient stream, which waits for the helper
-                    with torch.cuda.stream(side):
-                        works.append(dist.all_reduce(tiny, group=self.pg_c1, async_op=True))
-                blocked = _C.wait_blocks(self.lib, side, probe, main, helper, pre=pre) or blocked
-                with torch.cuda.stream(side):
-                    for w in works:
-                        w.wait()
-                torch.cuda.synchronize(self.dev)
-            v = torch.tensor([0.0 if blocked else 1.0], device=self.dev)
-            dist.all_reduce(v, op=dist.ReduceOp.MIN, group=self.pg)
-            if bool(v.item() == 1.0):
-                return True
-            if attempt < 3:
-                self.pg_c1 = dist.new_group(backend=dist.get_backend(self.pg))
-        return False
+    @native_comm.setter
+    def native_comm(self, comm):
+        self.small.native_comm = comm
 
-    def _overlap_after_step(self, i, main, side):
-        for j in self._bucket_at.get(i, ()):
-            self._launch_bucket(j, main, side)
+    @property
+    def native_comm_buckets(self):
+        return self.overlap.native_comm
 
-    def _launch_bucket(self, j, main, side):
-        lib, bkt = self.lib, self._buckets[j]
-        comm = side if side is not None else main   # the weight-gradient stream (or the only stream) carries the bucket work
-        if side is not None:
-            self._comm_events[j].record(main)
-            side.wait_event(self._comm_events[j])
-        self._bucket_stream = comm
-        cst = ctypes.c_void_p(comm.cuda_stream)
-        a = self._step_args
-        with torch.cuda.stream(comm):
-            _C.check(lib.rn_optim_clip_prepare(self.G.data_ptr(), self.P.data_ptr(), self.segs_dev.data_ptr(),
-                                               self.block_seg_dev.data_ptr(), self.n_blocks, bkt["block_begin"],
-                                               bkt["block_count"], a["wdc"], a["unscale"], self.L.data_ptr(),
-                                               self.opt_ws.data_ptr(), self.opt_ws.numel(), cst), "rn_optim_clip_prepare")
-            self._overlap_done += 1
-            if self._overlap_done == len(self._buckets):
-                assert j == 0
-                # every gradient of this rank is final: clip factors, metrics, and the two flags into G[0:2]
-                _C.check(lib.rn_optim_clip_factors(self.segs_dev.data_ptr(), self.n_segs, self.n_blocks, a["clip"],
-                                                   a["alpha"], self.metrics.data_ptr(), self.G.data_ptr(),
-                                                   self.opt_ws.data_ptr(), self.opt_ws.numel(), cst), "rn_optim_clip_factors")
-            if self.dp_active and self.native_comm_buckets is not None:
-                # rn_allreduce_bucket (rn_comm.hip): one ncclAllReduce on the bucket's stream, behind its prepare kernel
-                self.native_comm_buckets.all_reduce_bucket(self.G[bkt["begin"]:bkt["end"]])
-            elif self.dp_active:
-                import time as _time
-                import torch.distributed as dist
-                t0 = _time.perf_counter()
-                self._overlap_works.append(dist.all_reduce(self.G[bkt["begin"]:bkt["end"]], group=self.pg_c1,
-                                                           async_op=True))
-                self.bucket_host_ms = max(self.bucket_host_ms, (_time.perf_counter() - t0) * 1e3)
-        self._overlap_last_event = torch.cuda.Event()
-        self._overlap_last_event.record(comm)
-
-    def _overlap_finish(self, optimistic_sgd):
-        """After the join: wait for the buckets; when some rank's clip fired, all-reduce the correction.
-        optimistic_sgd: callable that enqueues the SGD kernel with the device-side predicate "G[0] == 0" (no clip fired on
-        any rank, no gradient non-finite: the common case).  The flag goes to pinned host memory with an asynchronous copy
-        enqueued BEFORE that kernel, the host waits for the copy's event only — the kernel runs while the host decides and
-        carries on enqueueing (a blocking `.item()` left the device idle for the host's wake-up and the next launches:
-        0.24 - 0.38 ms per step, bench.py's extra.dp_overhead).  Returns True when the optimistic kernel applied the step;
-        False when the flag fired (the kernel was a no-op: the caller runs the SGD kernel after the correction below)."""
-        cur = torch.cuda.current_stream(self.dev)
-        for w in self._overlap_works:
-            w.wait()
-        if self._bucket_stream is not None and self._bucket_stream != cur:
-            cur.wait_stream(self._bucket_stream)
-        applied = False
-        if self.price_without_flag_read:
-            fired = False                            # bench.py's extra.dp_overhead ONLY: what the host read below costs
-        else:
-            self._flag_host.copy_(self.G[0:1], non_blocking=True)
-            self._flag_event.record(cur)
-            optimistic_sgd()                         # predicate on the device: a no-op when G[0] != 0
-            self._flag_event.synchronize()
-            fired = float(self._flag_host[0]) != 0.0
-            applied = not fired
-        self.clip_fired = fired
-        if not fired:
-            return applied
-        st = _C.current_stream()
-        _C.check(self.lib.rn_optim_clip_apply(self.L.data_ptr(), self.L.data_ptr(), self.segs_dev.data_ptr(),
-                                              self.block_seg_dev.data_ptr(), self.n_blocks, self.opt_ws.data_ptr(),
-                                              self.opt_ws.numel(), st), "rn_optim_clip_apply")
-        self.L[:4].zero_()
-        if self.dp_active:
-            from retinanet.distribute import all_reduce_sum_bucketed
-            all_reduce_sum_bucketed(self.L, 2 if self.world == 1 else self.world, self.pg)   # (forced: issue it anyway)
-        self.G[4:].add_(self.L[4:])
-        return False
+    @native_comm_buckets.setter
+    def native_comm_buckets(self, comm):
+        self.overlap.native_comm = comm
 
     def optimizer_step(self, lr, momentum, clipnorm, wd_alpha, ema_decay, nesterov=False, overlapped=False):
         """weight decay + per-tensor / global clipping (executor.py:401-407) + all-reduce SUM (executor.py:436-437)
         + SGD momentum / moving average (optimizers/builder.py:45-54).  overlapped=True: backward() already sent the
-        buckets (see above); only the flag check / correction and the SGD kernel are left."""
+        buckets (GradientOverlap); only the flag check / correction and the SGD kernel are left."""
         lib, st = self.lib, _C.current_stream()
         unscale = 1.0 / self.loss_scale["scale"] if self.loss_scale else 1.0
         def sgd(skip_ptr):
@@ -2015,7 +1819,7 @@ class TrainEngine:
         if overlapped:
             # G[0] = sum over the ranks of "a clip factor != 1 or the gradient norm is not finite" (rn_optim_clip_factors:
             # a non-finite norm makes its factor != 1, so G[0] == 0 also says every gradient is finite)
-            applied = self._overlap_finish(lambda: sgd(self.G.data_ptr()))
+            applied = self.overlap.finish(lambda: sgd(self.G.data_ptr()), read_flag=not self.price_without_flag_read)
             if applied:
                 self.refresh_packs()
                 if self.loss_scale:
@@ -2091,16 +1895,8 @@ class TrainEngine:
         with torch.cuda.device(self.dev):
             alpha = cfg.weight_decay_alpha if cfg.use_weight_decay else 0.0
             self._prepack_dgrad_weights()
-            self._small_msgs = 0
-            self._c2_local, self._c2_sent, self.c2_normalizer = None, False, None
-            if self.sync_bn:    # sum(num-positives) + 1 of this rank (retinanet_loss.py:38): folded into SyncBN traffic
-                # (a device kernel reads it: a host tensor, or one on another GPU, must be moved first — ADVICE r4)
-                npos = targets["num-positives"].to(self.dev, torch.float32).contiguous()
-                self._c2_local = torch.empty((1,), dtype=torch.float32, device=self.dev)
-                _C.check(self.lib.rn_reduce_rows_f32(_C.ptr(npos), npos.numel(), 1, 1, 1.0, _C.ptr(self._c2_local),
-                                                     _C.current_stream()), "num-positives + 1")
+            self.small.begin_step(targets["num-positives"])
             preds = self.forward(images)
-            self._c2_local = None
             self._resolve_loss_scale()      # the previous step's "gradients not finite" flag: long since on the host
             step = self.step_count
             scale = self.loss_scale["scale"] if self.loss_scale else 1.0
@@ -2108,19 +1904,19 @@ class TrainEngine:
                                    clip=float(opt.clipnorm) if opt.clipnorm else 0.0)
             # per_replica_loss = total / replicas, times the loss scale under mixed_float16 (executor.py:421-425)
             loss = self.model.loss(targets, preds, compute_grads=True, grad_scale=scale / self.world,
-                                   grads_bf16=self.loss_grad_buffers(), normalizer=self.c2_normalizer)
+                                   grads_bf16=self.loss_grad_buffers(), normalizer=self.small.c2_normalizer)
             self._train_step_active = True
             try:
                 self.backward(None)
             finally:
                 self._train_step_active = False
-            overlapped = self._overlap_on      # backward() sent the gradient buckets as it completed them
-            if overlapped and self._overlap_done != len(self._buckets):
+            overlapped = self.overlap.on      # backward() sent the gradient buckets as it completed them
+            if overlapped and self.overlap.done != len(self.overlap.buckets):
                 raise RuntimeError("overlapped all-reduce: not every gradient bucket was launched")
             self.optimizer_step(opt.lr(step), opt.momentum, opt.clipnorm, alpha,
                                 opt.ema_decay(step) if opt.use_moving_average else None, nesterov=opt.nesterov,
                                 overlapped=overlapped)
-            self.syncbn_messages_per_step = self._small_msgs if self.sync_bn else 0
+            self.syncbn_messages_per_step = self.small.end_step()
             self.step_count += 1              # (taken back by _resolve_loss_scale when the step turns out dropped)
             opt.iterations = self.step_count
         out = dict(loss)

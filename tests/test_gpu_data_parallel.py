@@ -64,8 +64,8 @@ def _step(model, eng, images, targets):
             off, n = eng.p_off[k]
             gb[off:off + n] = True
     return {"P": eng.P.cpu().numpy(), "loss": float(out["weighted-loss"].item()), "gamma_beta": gb,
-            "norm_before_clip": float(eng.metrics[1].item()), "clip_fired": bool(getattr(eng, "clip_fired", False)),
-            "overlapped": bool(eng._overlap_on), "l2": float(out["l2-regularization"].item()),
+            "norm_before_clip": float(eng.metrics[1].item()), "clip_fired": bool(eng.overlap.clip_fired),
+            "overlapped": bool(eng.overlap.on), "l2": float(out["l2-regularization"].item()),
             "mm": {k: v["mm"].cpu().numpy() for k, v in eng.bn_state.items()}}
 
 
@@ -76,7 +76,7 @@ def _worker(rank, world, port, out):
     assert eng.sync_bn
     out[rank] = _step(model, eng, images, targets)
     assert out[rank]["overlapped"]                 # the default N > 1 path: buckets go out during the backward pass
-    assert eng.c2_normalizer is not None           # ... and the loss normaliser rode in the first SyncBN message
+    assert eng.small.c2_normalizer is not None     # ... and the loss normaliser rode in the first SyncBN message
     dist.destroy_process_group()
 
 
@@ -215,7 +215,7 @@ def _worker_forced_dp(rank, world, port, out):
         r["sync_bn"], r["native"] = bool(eng.sync_bn), native is not None
         r["native_buckets"] = getattr(eng, "native_comm_buckets", None) is not None
         r["messages"] = eng.syncbn_messages_per_step
-        r["overlap_unsafe"] = bool(getattr(eng, "_overlap_unsafe", False))
+        r["overlap_unsafe"] = bool(eng.overlap.unsafe)
         r["side_stream_probed"] = getattr(eng, "side_stream_probed", None)
         res[tag] = r
         if native is not None:

@@ -216,7 +216,7 @@ def test_two_stream_backward_is_bit_identical(cuda):
     bit — a race on dy, a saved activation or a workspace would show up as a difference."""
     p, model, eng, targets, images = _setup(cuda, 256, 4, True, freeze=True)
     assert eng.side_stream_on
-    assert any(getattr(fn, "side", False) for fn in eng.bwd_steps)
+    assert any(step.side for step in eng.bwd_steps)
     preds = eng.forward(images.to(cuda))
     g = torch.Generator().manual_seed(99)
     up = {k: {lv: torch.randn(preds[k][lv].shape, generator=g).to(cuda) for lv in preds[k]} for k in preds}

@@ -31,8 +31,7 @@ def grads_once(eng, model, images, targets):
     with torch.cuda.device(eng.dev):
         eng._step_args = dict(wdc=0.0, alpha=0.0, unscale=1.0, clip=0.0)
         eng._prepack_dgrad_weights()
-        eng._small_msgs = 0
-        eng._c2_local, eng._c2_sent, eng.c2_normalizer = None, False, None
+        eng.small.begin_step(targets["num-positives"])
         preds = eng.forward(images)
         logits = {l: preds["class-predictions"][l].clone() for l in preds["class-predictions"]}
         loss = model.loss(targets, preds, compute_grads=True, grad_scale=1.0, grads_bf16=eng.loss_grad_buffers(),

@@ -11,7 +11,7 @@ from bench import synth_ground_truth
 from retinanet.cfg import efficientnet_params
 from retinanet.dataloader import LabelEncoder
 from retinanet.model import ModelBuilder
-from retinanet.model.train_engine import TrainEngine
+from retinanet.model.train_engine import BackwardStep, TrainEngine
 
 dev = torch.device("cuda:0")
 p = efficientnet_params("efficientnet-b3", input_size=640)
@@ -36,10 +36,7 @@ def wrap(lst, tag):
             r = fn(st)
             acc[(tag, i)].append((time.perf_counter() - t0) * 1e6)
             return r
-        for a in ("side", "writes", "name"):
-            if hasattr(fn, a):
-                setattr(w, a, getattr(fn, a))
-        out.append(w)
+        out.append(BackwardStep(w, fn.side, fn.writes))
     return out
 
 
@@ -54,5 +51,5 @@ rows = sorted(((sum(v[1:]) / len(v[1:]), k) for k, v in acc.items()), reverse=Tr
 print("host us in backward closures:", round(sum(r[0] for r in rows)))
 for us, k in rows[:12]:
     fn = orig[k[1]]
-    print(k, round(us, 1), "side" if getattr(fn, "side", False) else "main", fn.__qualname__.split(".")[-1],
-          (getattr(fn, "writes", None) or [""])[0][:60], [round(x) for x in acc[k]])
+    print(k, round(us, 1), "side" if fn.side else "main", fn.run.__qualname__.split(".")[-1],
+          (fn.writes or [""])[0][:60], [round(x) for x in acc[k]])

@@ -11,8 +11,8 @@ b=ModelBuilder(p,'train',device=dev,seed=1337); m=b()
 rx=[b.FREEZE_VARS_REGEX[n] for n in p.training.freeze_variables]
 eng=TrainEngine(m,32,frozen_regexes=rx,world_size=1)
 steps=eng.bwd_steps
-last_main=max(i for i,f in enumerate(steps) if not getattr(f,'side',False))
+last_main=max(i for i,f in enumerate(steps) if not f.side)
 print('steps',len(steps),'last main',last_main)
 for i in range(max(0,len(steps)-30),len(steps)):
     f=steps[i]
-    print(i,'side' if getattr(f,'side',False) else 'MAIN', getattr(f,'writes',[])[:3], f.__name__ if hasattr(f,'__name__') else '')
+    print(i,'side' if f.side else 'MAIN', list(f.writes)[:3], f.run.__name__)

@@ -53,7 +53,7 @@ def main():
     from retinanet.cfg import default_params
     from retinanet.dataloader import LabelEncoder
     from retinanet.model import ModelBuilder
-    from retinanet.model.train_engine import TrainEngine
+    from retinanet.model.train_engine import BackwardStep, TrainEngine
     from retinanet.optimizers import build_optimizer
     dev = torch.device("cuda:0")
     p = default_params(input_size=a.size)
@@ -79,7 +79,7 @@ def main():
             rec.append((phase, label, e0, e1))
         return g
     eng.fwd_steps = [wrap(f, "fwd") for f in eng.fwd_steps]
-    eng.bwd_steps = [wrap(f, "bwd") for f in eng.bwd_steps]
+    eng.bwd_steps = [BackwardStep(wrap(f.run, "bwd")) for f in eng.bwd_steps]   # every step on the main stream
     eng.train_step(images, targets)
     torch.cuda.synchronize()
     rows = [(ph, lb[0], e0.elapsed_time(e1), lb[1], lb[2]) for ph, lb, e0, e1 in rec]
