@@ -142,9 +142,10 @@ optim_factors_kernel(const OptSeg* __restrict__ segs, int nseg, const double* __
 }
 
 // g <- g * factor[tensor] in place (out == nullptr), or out <- (factor[tensor] - 1) * g: the correction this rank
-// owes an all-reduce that already summed its UNclipped gradients (the optimistic-clip overlap, see rn_optim_clip_*)
+// owes an all-reduce that already summed its UNclipped gradients (the optimistic-clip overlap, see rn_optim_clip_*).
+// g and out are not __restrict__: the engine takes the correction in place (out == g, data_parallel.py finish()).
 __global__ void __launch_bounds__(OPT_THREADS)
-optim_scale_kernel(float* __restrict__ g, float* __restrict__ out, const OptSeg* __restrict__ segs,
+optim_scale_kernel(float* g, float* out, const OptSeg* __restrict__ segs,
                    const int* __restrict__ block_seg, const float* __restrict__ factor) {
   const int si = block_seg[blockIdx.x];
   const OptSeg s = segs[si];

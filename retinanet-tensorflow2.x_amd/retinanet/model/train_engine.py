@@ -1817,8 +1817,9 @@ class TrainEngine:
                                            lr, momentum, ema_decay if ema_decay is not None else 0.0, 1 if nesterov else 0,
                                            skip_ptr, st), "rn_optim_sgd_step")
         if overlapped:
-            # G[0] = sum over the ranks of "a clip factor != 1 or the gradient norm is not finite" (rn_optim_clip_factors:
-            # a non-finite norm makes its factor != 1, so G[0] == 0 also says every gradient is finite)
+            # G[0] = sum over the ranks of "a clip factor != 1 or the gradient norm is not finite".  A NaN norm leaves every
+            # factor at 1 (fmaxf drops it): rn_optim_clip_factors tests the global norm for finiteness on its own and
+            # sets flags[0] then too, so G[0] == 0 also says every gradient is finite
             applied = self.overlap.finish(lambda: sgd(self.G.data_ptr()), read_flag=not self.price_without_flag_read)
             if applied:
                 self.refresh_packs()
