@@ -665,6 +665,45 @@ int rn_optim_sgd_step(float* params, const float* grads, float* momentum_buf, fl
                       const void* segs_dev, const int32_t* block_seg_dev, int num_blocks, float lr, float momentum,
                       float ema_decay, int nesterov, const float* skip_flag, void* stream);
 
+/*
+ * Adam, RMSprop and Adagrad of Keras optimizer_v2 (TF 2.8) over the same arenas, segment table and blocks as
+ * rn_optim_sgd_step, with the same access rules: 16 bytes per lane and array where the fp32 offset and the 16-bit offset
+ * of a block are multiples of 4, a scalar tail, a scalar loop for other offsets; nothing outside tensor elements is
+ * written; skip_flag (device f32, may be NULL) non-zero = no array changes; ema == NULL = no moving average; the 16-bit
+ * copy is the cast of the kernel's own new fp32 weight.  Every line below is evaluated in fp32 in the order written,
+ * each product, sum, root and quotient rounded once; 1 - beta1, 1 - beta2, 1 - rho and 1 - ema_decay are fp32
+ * differences formed on the device.
+ *   RN_OPT_ADAM      slot0 = m, slot1 = v, slot2 = vhat (RN_OPT_AMSGRAD only)
+ *       m  = m + (g - m) * (1 - beta1)
+ *       v  = v + (g * g - v) * (1 - beta2)
+ *       vhat = fmaxf(vhat, v) and d = vhat with RN_OPT_AMSGRAD, d = v without
+ *       w  = w - (lr * m) / (sqrtf(d) + epsilon)
+ *     rule.lr is alpha_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), t = iterations + 1, formed by the caller.
+ *   RN_OPT_RMSPROP   slot0 = rms, slot1 = momentum (RN_OPT_MOMENTUM only), slot2 = mg (RN_OPT_CENTERED only)
+ *       rms = rms + (g * g - rms) * (1 - rho)
+ *       mg  = mg + (g - mg) * (1 - rho) and d = rms - mg * mg with RN_OPT_CENTERED, d = rms without
+ *     with RN_OPT_MOMENTUM (Keras momentum > 0, the fused op: epsilon inside the root)
+ *       mom = momentum * mom + (lr * g) / sqrtf(d + epsilon)
+ *       w   = w - mom
+ *     without (Keras momentum == 0: epsilon outside the root)
+ *       w   = w - (lr * g) / (sqrtf(d) + epsilon)
+ *   RN_OPT_ADAGRAD   slot0 = accumulator (the caller fills it with initial_accumulator_value before the first step)
+ *       acc = acc + g * g
+ *       w   = w - (lr * g) / (sqrtf(acc) + epsilon)
+ *   all rules, ema != NULL:  ema = ema - (1 - ema_decay) * (ema - w), w the new weight
+ * A slot the rule does not use is neither read nor written and may be NULL.  RN_EINVAL before any launch: an unknown
+ * rule, a flag that does not belong to the rule, a missing slot array the rule needs.
+ */
+enum { RN_OPT_ADAM = 1, RN_OPT_RMSPROP = 2, RN_OPT_ADAGRAD = 3 };
+enum { RN_OPT_AMSGRAD = 1, RN_OPT_CENTERED = 2, RN_OPT_MOMENTUM = 4 };
+typedef struct {
+  int32_t rule, flags;
+  float lr, beta1, beta2, rho, momentum, epsilon, ema_decay;
+} rn_optim_rule;
+int rn_optim_step(float* params, const float* grads, float* slot0, float* slot1, float* slot2, float* ema,
+                  void* params_bf16, const void* segs_dev, const int32_t* block_seg_dev, int num_blocks,
+                  const rn_optim_rule* rule /* host */, const float* skip_flag, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * C1-C3  collectives of the data-parallel step over RCCL / xGMI (the reference reaches them through
  * tf.distribute: retinanet_loss.py:46-49, model/utils.py:10-12, executor.py:436-437).  One process per GPU; rank 0

@@ -10,6 +10,7 @@
 //   stage 4  Keras SGD momentum  v <- m v - lr g ; w <- w + v   (optimizers/builder.py:45)
 //            tfa MovingAverage   ema <- ema - (1-d)(ema - w)    (optimizers/builder.py:51-54)
 //            and the bf16 compute copy of w for the next forward.
+//            training.optimizer.name = adam | rmsprop | adagrad: the Keras rule instead of SGD (rn_optim_step)
 // Deterministic: block partials are added in index order.  HBM-bound: 34.4 M params.
 #include "rn_common.h"
 
@@ -315,6 +316,174 @@ extern "C" int rn_optim_sgd_step(float* params, const float* grads, float* momen
   hipLaunchKernelGGL(optim_sgd_kernel, dim3(num_blocks), dim3(OPT_THREADS), 0, (hipStream_t)stream, params, grads,
                      momentum_buf, ema, (uint16_t*)params_bf16, (const OptSeg*)segs_dev, block_seg_dev, lr, momentum,
                      ema_decay, ema ? 1 : 0, nesterov, skip_flag);
+  RN_CHECK_LAUNCH();
+  return RN_OK;
+}
+
+// ---- Adam / RMSprop / Adagrad (Keras optimizer_v2; the contract with its op order is in include/rnet_hip.h) ----------
+// The same walk as optim_sgd_kernel: one block per OPT_CHUNK elements of one tensor, 16 bytes per lane and array where
+// the fp32 and the 16-bit offset allow it, a scalar tail, a scalar loop for every other offset.  The rule, its flags and
+// the moving average are template parameters: the element loop has no branch on them, and a slot the rule does not use
+// is neither read nor written (its pointer may be NULL).
+struct OptK { float lr, c1, c2, momentum, eps, omd; };   // c1 = 1 - beta1 | 1 - rho, c2 = 1 - beta2, omd = 1 - ema_decay
+
+template <int RULE, int FLAGS>
+struct OptUse {
+  static constexpr bool s1 = RULE == RN_OPT_ADAM || (RULE == RN_OPT_RMSPROP && (FLAGS & RN_OPT_MOMENTUM));
+  static constexpr bool s2 = (RULE == RN_OPT_ADAM && (FLAGS & RN_OPT_AMSGRAD)) ||
+                             (RULE == RN_OPT_RMSPROP && (FLAGS & RN_OPT_CENTERED));
+};
+
+// every line is one rounded fp32 operation or two (-ffp-contract=off, correctly rounded sqrt and divide)
+template <int RULE, int FLAGS, bool EMA>
+__device__ __forceinline__ void optim_rule_elem(float& w, const float g, float& s0, float& s1, float& s2, float& e,
+                                                const OptK& k) {
+  float nw;
+  if constexpr (RULE == RN_OPT_ADAM) {
+    const float m = s0 + (g - s0) * k.c1;
+    const float v = s1 + (g * g - s1) * k.c2;
+    float den = v;
+    if constexpr ((FLAGS & RN_OPT_AMSGRAD) != 0) {
+      den = fmaxf(s2, v);
+      s2 = den;
+    }
+    s0 = m;
+    s1 = v;
+    nw = w - (k.lr * m) / (sqrtf(den) + k.eps);
+  } else if constexpr (RULE == RN_OPT_RMSPROP) {
+    const float ms = s0 + (g * g - s0) * k.c1;
+    s0 = ms;
+    float den = ms;
+    if constexpr ((FLAGS & RN_OPT_CENTERED) != 0) {
+      const float mg = s2 + (g - s2) * k.c1;
+      s2 = mg;
+      den = ms - mg * mg;
+    }
+    if constexpr ((FLAGS & RN_OPT_MOMENTUM) != 0) {   // the fused op: epsilon inside the root
+      const float mom = k.momentum * s1 + (k.lr * g) / sqrtf(den + k.eps);
+      s1 = mom;
+      nw = w - mom;
+    } else {                                          // Keras' own formula: epsilon outside the root
+      nw = w - (k.lr * g) / (sqrtf(den) + k.eps);
+    }
+  } else {
+    const float acc = s0 + g * g;
+    s0 = acc;
+    nw = w - (k.lr * g) / (sqrtf(acc) + k.eps);
+  }
+  w = nw;
+  if constexpr (EMA) e = e - k.omd * (e - nw);
+}
+
+template <int RULE, int FLAGS, bool EMA>
+__global__ void __launch_bounds__(OPT_THREADS)
+optim_rule_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
+                  float* __restrict__ s2, float* __restrict__ ema, uint16_t* __restrict__ wbf16,
+                  const OptSeg* __restrict__ segs, const int* __restrict__ block_seg, const rn_optim_rule r,
+                  const float* __restrict__ skip_flag) {
+  if (skip_flag && skip_flag[0] != 0.0f) return;
+  constexpr bool U1 = OptUse<RULE, FLAGS>::s1, U2 = OptUse<RULE, FLAGS>::s2;
+  const int si = block_seg[blockIdx.x];
+  const OptSeg s = segs[si];
+  const long long b0 = (long long)(blockIdx.x - s.block_begin) * OPT_CHUNK;
+  long long b1 = b0 + OPT_CHUNK;
+  if (b1 > s.size) b1 = s.size;
+  OptK k;
+  k.lr = r.lr;
+  k.c1 = 1.0f - (RULE == RN_OPT_ADAM ? r.beta1 : r.rho);
+  k.c2 = 1.0f - r.beta2;
+  k.momentum = r.momentum;
+  k.eps = r.epsilon;
+  k.omd = 1.0f - r.ema_decay;
+  auto one = [&](const long long i) {   // element i of the tensor, scalar accesses
+    const long long o = s.offset + i;
+    float wv = w[o], av = s0[o], bv = 0.0f, cv = 0.0f, ev = 0.0f;
+    if constexpr (U1) bv = s1[o];
+    if constexpr (U2) cv = s2[o];
+    if constexpr (EMA) ev = ema[o];
+    optim_rule_elem<RULE, FLAGS, EMA>(wv, g[o], av, bv, cv, ev, k);
+    s0[o] = av;
+    if constexpr (U1) s1[o] = bv;
+    if constexpr (U2) s2[o] = cv;
+    w[o] = wv;
+    if constexpr (EMA) ema[o] = ev;
+    if (s.bf16_offset >= 0) wbf16[s.bf16_offset + i] = rn_f32_to_bf16(wv);
+  };
+  const bool vec = ((s.offset + b0) & 3) == 0 && (s.bf16_offset < 0 || ((s.bf16_offset + b0) & 3) == 0);
+  if (vec) {   // 16 bytes per lane and array; scalar tail
+    const long long base = s.offset + b0;
+    const int n = (int)(b1 - b0), n4 = n >> 2;
+    float4* w4 = (float4*)(w + base);
+    const float4* g4 = (const float4*)(g + base);
+    float4* a4 = (float4*)(s0 + base);
+    float4* b4 = U1 ? (float4*)(s1 + base) : nullptr;
+    float4* c4 = U2 ? (float4*)(s2 + base) : nullptr;
+    float4* e4 = EMA ? (float4*)(ema + base) : nullptr;
+    uint2* h4 = s.bf16_offset >= 0 ? (uint2*)(wbf16 + s.bf16_offset + b0) : nullptr;
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int i = threadIdx.x; i < n4; i += OPT_THREADS) {
+      float4 wv = w4[i], av = a4[i], bv = zero, cv = zero, ev = zero;
+      const float4 gv = g4[i];
+      if constexpr (U1) bv = b4[i];
+      if constexpr (U2) cv = c4[i];
+      if constexpr (EMA) ev = e4[i];
+      optim_rule_elem<RULE, FLAGS, EMA>(wv.x, gv.x, av.x, bv.x, cv.x, ev.x, k);
+      optim_rule_elem<RULE, FLAGS, EMA>(wv.y, gv.y, av.y, bv.y, cv.y, ev.y, k);
+      optim_rule_elem<RULE, FLAGS, EMA>(wv.z, gv.z, av.z, bv.z, cv.z, ev.z, k);
+      optim_rule_elem<RULE, FLAGS, EMA>(wv.w, gv.w, av.w, bv.w, cv.w, ev.w, k);
+      a4[i] = av;
+      if constexpr (U1) b4[i] = bv;
+      if constexpr (U2) c4[i] = cv;
+      w4[i] = wv;
+      if constexpr (EMA) e4[i] = ev;
+      if (h4) h4[i] = make_uint2((unsigned)rn_f32_to_bf16(wv.x) | ((unsigned)rn_f32_to_bf16(wv.y) << 16),
+                                 (unsigned)rn_f32_to_bf16(wv.z) | ((unsigned)rn_f32_to_bf16(wv.w) << 16));
+    }
+    if ((int)threadIdx.x < (n & 3)) one(b0 + 4 * n4 + threadIdx.x);   // the tail: fewer than 4 elements, one lane each
+  } else {
+    for (long long i = b0 + threadIdx.x; i < b1; i += OPT_THREADS) one(i);
+  }
+}
+
+extern "C" int rn_optim_step(float* params, const float* grads, float* slot0, float* slot1, float* slot2, float* ema,
+                             void* params_bf16, const void* segs_dev, const int32_t* block_seg_dev, int num_blocks,
+                             const rn_optim_rule* rule, const float* skip_flag, void* stream) {
+  RN_CHECK_ARG(params && grads && segs_dev && block_seg_dev && num_blocks > 0 && rule, "rn_optim_step: bad argument");
+  const int allowed = rule->rule == RN_OPT_ADAM ? RN_OPT_AMSGRAD
+                      : rule->rule == RN_OPT_RMSPROP ? (RN_OPT_CENTERED | RN_OPT_MOMENTUM)
+                      : rule->rule == RN_OPT_ADAGRAD ? 0 : -1;
+  RN_CHECK_ARG(allowed >= 0, "rn_optim_step: unknown rule %d", rule->rule);
+  RN_CHECK_ARG((rule->flags & ~allowed) == 0, "rn_optim_step: rule %d does not take flags 0x%x", rule->rule, rule->flags);
+  const bool need1 = rule->rule == RN_OPT_ADAM || (rule->flags & RN_OPT_MOMENTUM);
+  const bool need2 = (rule->flags & (RN_OPT_AMSGRAD | RN_OPT_CENTERED)) != 0;
+  RN_CHECK_ARG(slot0 && (!need1 || slot1) && (!need2 || slot2), "rn_optim_step: rule %d flags 0x%x: a slot array is missing",
+               rule->rule, rule->flags);
+  const hipStream_t st = (hipStream_t)stream;
+  const OptSeg* segs = (const OptSeg*)segs_dev;
+  uint16_t* h16 = (uint16_t*)params_bf16;
+#define OPT_LAUNCH(R_, F_)                                                                                              \
+  do {                                                                                                                  \
+    if (ema)                                                                                                            \
+      hipLaunchKernelGGL((optim_rule_kernel<R_, F_, true>), dim3(num_blocks), dim3(OPT_THREADS), 0, st, params, grads,  \
+                         slot0, slot1, slot2, ema, h16, segs, block_seg_dev, *rule, skip_flag);                         \
+    else                                                                                                                \
+      hipLaunchKernelGGL((optim_rule_kernel<R_, F_, false>), dim3(num_blocks), dim3(OPT_THREADS), 0, st, params, grads, \
+                         slot0, slot1, slot2, ema, h16, segs, block_seg_dev, *rule, skip_flag);                         \
+  } while (0)
+  if (rule->rule == RN_OPT_ADAM) {
+    if (rule->flags & RN_OPT_AMSGRAD) OPT_LAUNCH(RN_OPT_ADAM, RN_OPT_AMSGRAD);
+    else OPT_LAUNCH(RN_OPT_ADAM, 0);
+  } else if (rule->rule == RN_OPT_RMSPROP) {
+    switch (rule->flags) {
+      case 0: OPT_LAUNCH(RN_OPT_RMSPROP, 0); break;
+      case RN_OPT_CENTERED: OPT_LAUNCH(RN_OPT_RMSPROP, RN_OPT_CENTERED); break;
+      case RN_OPT_MOMENTUM: OPT_LAUNCH(RN_OPT_RMSPROP, RN_OPT_MOMENTUM); break;
+      default: OPT_LAUNCH(RN_OPT_RMSPROP, RN_OPT_CENTERED | RN_OPT_MOMENTUM); break;
+    }
+  } else {
+    OPT_LAUNCH(RN_OPT_ADAGRAD, 0);
+  }
+#undef OPT_LAUNCH
   RN_CHECK_LAUNCH();
   return RN_OK;
 }

@@ -22,7 +22,9 @@ RN_ACT_NONE, RN_ACT_RELU, RN_ACT_RELU6, RN_ACT_SWISH = 0, 1, 2, 3
 RN_FUSION_FAST_ATTENTION, RN_FUSION_FAST_CHANNEL_ATTENTION = 1, 2
 FUSION_IDS = {"fast_attention": RN_FUSION_FAST_ATTENTION, "fast_channel_attention": RN_FUSION_FAST_CHANNEL_ATTENTION}
 RN_CONV_MAX_SEGMENTS = 10
-ABI_VERSION = 10
+ABI_VERSION = 11
+RN_OPT_ADAM, RN_OPT_RMSPROP, RN_OPT_ADAGRAD = 1, 2, 3            # rn_optim_rule.rule
+RN_OPT_AMSGRAD, RN_OPT_CENTERED, RN_OPT_MOMENTUM = 1, 2, 4       # rn_optim_rule.flags
 # f32 kernels of the dtype=float32 prediction convs (detection_head.py:80-88) as split-bf16 planes (rn_conv_segment.w_terms)
 PRED_W_TERMS = int(os.environ.get("RNET_PRED_W_TERMS", "2"))
 ACT_IDS = {None: RN_ACT_NONE, "none": RN_ACT_NONE, "relu": RN_ACT_RELU, "relu6": RN_ACT_RELU6,
@@ -61,6 +63,11 @@ class LaunchOpts(Structure):   # rn_launch_opts: per-call options of the MFMA ke
         for k, v in kw.items():
             setattr(o, k, int(v))
         return o
+
+
+class OptimRule(Structure):   # rn_optim_rule
+    _fields_ = [("rule", c_int32), ("flags", c_int32), ("lr", c_float), ("beta1", c_float), ("beta2", c_float),
+                ("rho", c_float), ("momentum", c_float), ("epsilon", c_float), ("ema_decay", c_float)]
 
 
 class Bottleneck64Problem(Structure):   # rn_bottleneck64_problem
@@ -246,6 +253,8 @@ _SIGNATURES = {
     "rn_optim_clip_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "rn_optim_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
+    "rn_optim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_int, POINTER(OptimRule), c_void_p, c_void_p]),
     "rn_prepare_image": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, POINTER(c_float),
                                  POINTER(c_float), c_float, c_void_p]),
     "rn_bottleneck64_supported": (c_int, [c_int, c_int, c_int, c_int]),

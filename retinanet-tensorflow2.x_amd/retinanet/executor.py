@@ -266,8 +266,8 @@ class Executor:
                 self._loaded_slots = {}
             else:
                 self._loaded_slots = self._model.load_weights(latest)
-                it = self._model.loaded_extras.get("SGD/iter")
-                self.optimizer.iterations = int(it) if it is not None else 0
+                from retinanet.optimizers.builder import read_iterations
+                self.optimizer.iterations = read_iterations(self._model.loaded_extras, self.optimizer)[0]
             self.restore_status = _RestoreStatus(before - set(self._model.variables))
             return
         if "export" in self.run_mode:

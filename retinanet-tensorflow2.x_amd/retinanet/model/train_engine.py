@@ -401,7 +401,12 @@ class TrainEngine:
         self.n_params = off
         self.P = torch.zeros((off,), dtype=torch.float32, device=self.dev)
         self.G = torch.zeros_like(self.P)
+        # optimizer slots: V is the step kernel's slot 0 (SGD `momentum`, Adam `m`, RMSprop `rms`, Adagrad `accumulator`);
+        # S1 / S2 exist only while the configured rule has a second / third slot (_bind_optimizer)
         self.V = torch.zeros_like(self.P)
+        self.S1 = self.S2 = None
+        self._slot_spec = [("momentum", 0.0), None, None]
+        self._slot_owner = "sgd"
         self.E = torch.zeros_like(self.P)
         self.Pbf = torch.zeros((max(bf_off, 8),), dtype=self.h16, device=self.dev)
         self._bf_copies = [(self.p_off[k], s[6]) for k, s in zip(names, segs) if s[6] >= 0]
@@ -439,10 +444,39 @@ class TrainEngine:
             t = self._to_compute_layout(k, v[k].to(self.dev, torch.float32))
             self._pview(k).copy_(t.reshape(-1))
         self.E.copy_(self.P)
-        self.V.zero_()
+        self._bind_optimizer(reset=True)
         for (off, n), bfo in self._bf_copies:
             self.Pbf[bfo:bfo + n].copy_(self.P[off:off + n])
         self.refresh_packs()
+
+    def _bind_optimizer(self, reset=False):
+        """Slot arenas for the optimizer the model holds NOW (tests and tools replace `model.optimizer` after the engine
+        is built): one arena per slot of its rule and no more — SGD keeps exactly V.  A rule or slot set other than the
+        bound one (re)allocates and starts every slot at its initial value (Adagrad's accumulator: 0.1); reset=True
+        does the latter on its own."""
+        opt = getattr(self.model, "optimizer", None)
+        owner = opt.name if opt is not None else "sgd"
+        spec = list(opt.slots()) if opt is not None else [("momentum", 0.0)]
+        spec += [None] * (3 - len(spec))
+        changed = (owner, spec) != (self._slot_owner, self._slot_spec)
+        if changed:
+            self._slot_owner, self._slot_spec = owner, spec
+            self.S1 = (self.S1 if self.S1 is not None else torch.zeros_like(self.P)) if spec[1] else None
+            self.S2 = (self.S2 if self.S2 is not None else torch.zeros_like(self.P)) if spec[2] else None
+        if changed or reset:
+            for arena, s in zip((self.V, self.S1, self.S2), self._slot_spec):
+                if s is not None:
+                    arena.fill_(s[1])
+        return opt
+
+    def _slot_arena(self, slot):
+        """the arena that holds Keras slot `slot` of the bound optimizer (`average`: the moving average), or None"""
+        if slot == "average":
+            return self.E
+        for arena, s in zip((self.V, self.S1, self.S2), self._slot_spec):
+            if s is not None and s[0] == slot:
+                return arena
+        return None
 
     def _stem_op(self):
         return next(o for o in self.ops if o["op"] == "stem")
@@ -482,24 +516,32 @@ class TrainEngine:
         return t.reshape(v.shape)
 
     def optimizer_slots(self):
-        """{(variable, slot): f32 array}: the SGD `momentum` accumulators and the moving-average `average` copies
+        """{(variable, slot): f32 array}: the optimizer's slots under their Keras names (SGD `momentum`; Adam `m`, `v`,
+        `vhat`; RMSprop `rms`, `momentum`, `mg`; Adagrad `accumulator`) and the moving-average `average` copies
         (optimizers/builder.py:27-71 — what `save_weights` stores next to the weights for a resume)."""
+        self._bind_optimizer()
         out = {}
         for k in self.train_names:
-            out[(k, "momentum")] = self._keras_layout(k, self.V).detach().cpu().numpy().copy()
+            for arena, s in zip((self.V, self.S1, self.S2), self._slot_spec):
+                if s is not None:
+                    out[(k, s[0])] = self._keras_layout(k, arena).detach().cpu().numpy().copy()
             out[(k, "average")] = self._keras_layout(k, self.E).detach().cpu().numpy().copy()
         return out
 
-    def load_optimizer_slots(self, slots):
-        """Inverse of `optimizer_slots`; variables without a stored slot keep their current state."""
+    def load_optimizer_slots(self, slots, only=None):
+        """Inverse of `optimizer_slots`; variables without a stored slot keep their current state, and so do slots the
+        bound optimizer does not have.  only: restrict to these slot names."""
+        self._bind_optimizer()
         for (k, slot), arr in slots.items():
-            if k not in self.p_off or slot not in ("momentum", "average"):
+            arena = self._slot_arena(slot)
+            if k not in self.p_off or arena is None or (only is not None and slot not in only):
                 continue
             t = self._to_compute_layout(k, torch.as_tensor(np.asarray(arr), dtype=torch.float32).to(self.dev))
-            self._pview(k, self.V if slot == "momentum" else self.E).copy_(t.reshape(-1))
+            self._pview(k, arena).copy_(t.reshape(-1))
 
     def save_checkpoint(self, prefix):
-        """Weights + BN moving statistics + optimizer slots (`momentum`, `average`) + the step counter, in
+        """Weights + BN moving statistics + optimizer slots (SGD `momentum`, Adam `m` / `v` / `vhat`, RMSprop `rms` /
+        `momentum` / `mg`, Adagrad `accumulator`; `average`) + the step counter (`<Class>/iter`), in
         TensorFlow's checkpoint FILE format (where executor.py:652-654 / 695-697 call `model.save_weights`).  Interop
         is one-way: this build reads what the reference wrote (by variable name through the object graph); the
         reference's Keras `load_weights` matches structurally and will not consume the flat object graph written
@@ -508,7 +550,8 @@ class TrainEngine:
             self.store_to_model(use_ema=False)
             torch.cuda.synchronize()
         self.finish_step()
-        extra = {"SGD/iter": np.asarray(self.step_count, dtype=np.int64)}
+        from retinanet.optimizers.builder import iter_key
+        extra = {iter_key(self.model.optimizer): np.asarray(self.step_count, dtype=np.int64)}   # SGD/iter, Adam/iter, ...
         if self.loss_scale:   # Keras' LossScaleOptimizer checkpoints its dynamic state the same way
             extra["loss_scale/current_loss_scale"] = np.asarray(self.loss_scale["scale"], dtype=np.float32)
             extra["loss_scale/good_steps"] = np.asarray(self.loss_scale["good"], dtype=np.int64)
@@ -523,10 +566,19 @@ class TrainEngine:
                 d["mm"].copy_(self.model.variables[bn + "/moving_mean"])
                 d["mv"].copy_(self.model.variables[bn + "/moving_variance"])
             self._fold_frozen()
-            self.load_optimizer_slots(slots)
-            it = self.model.loaded_extras.get("SGD/iter")
+            from retinanet.optimizers.builder import iter_key, read_iterations
+            it, wrote = read_iterations(self.model.loaded_extras, self.model.optimizer)
+            mine = iter_key(self.model.optimizer)[:-len("/iter")]
+            if wrote in (None, mine):
+                self.load_optimizer_slots(slots)
+            else:   # another optimizer wrote the file: its slots mean nothing to this one (and may share a name)
+                import logging
+                logging.warning("checkpoint %s was written by %s, the configured optimizer is %s: weights, moving "
+                                "averages and the step counter are restored, %s starts with fresh slots", prefix, wrote,
+                                mine, mine)
+                self.load_optimizer_slots(slots, only=("average",))
             self._ls_pending = False
-            self.step_count = int(it) if it is not None else 0
+            self.step_count = it
             if self.model.optimizer is not None:
                 self.model.optimizer.iterations = self.step_count
             ls = self.model.loaded_extras.get("loss_scale/current_loss_scale")
@@ -1804,18 +1856,42 @@ class TrainEngine:
     def native_comm_buckets(self, comm):
         self.overlap.native_comm = comm
 
-    def optimizer_step(self, lr, momentum, clipnorm, wd_alpha, ema_decay, nesterov=False, overlapped=False):
+    def _optim_rule(self, opt, lr, ema_decay):
+        """rn_optim_rule of an Adam / RMSprop / Adagrad configuration; lr is the kernel's scalar (OptimizerConfig.step_size)"""
+        rule = {"adam": _C.RN_OPT_ADAM, "rmsprop": _C.RN_OPT_RMSPROP, "adagrad": _C.RN_OPT_ADAGRAD}[opt.name]
+        flags = 0
+        if opt.name == "adam" and opt.amsgrad:
+            flags |= _C.RN_OPT_AMSGRAD
+        if opt.name == "rmsprop":
+            flags |= (_C.RN_OPT_CENTERED if opt.centered else 0) | (_C.RN_OPT_MOMENTUM if opt.momentum > 0.0 else 0)
+        return _C.OptimRule(rule=rule, flags=flags, lr=lr, beta1=opt.beta_1, beta2=opt.beta_2, rho=opt.rho,
+                            momentum=opt.momentum, epsilon=opt.epsilon,
+                            ema_decay=ema_decay if ema_decay is not None else 0.0)
+
+    def optimizer_step(self, lr, momentum, clipnorm, wd_alpha, ema_decay, nesterov=False, overlapped=False, opt=None):
         """weight decay + per-tensor / global clipping (executor.py:401-407) + all-reduce SUM (executor.py:436-437)
-        + SGD momentum / moving average (optimizers/builder.py:45-54).  overlapped=True: backward() already sent the
-        buckets (GradientOverlap); only the flag check / correction and the SGD kernel are left."""
+        + the update rule / moving average (optimizers/builder.py:45-54).  overlapped=True: backward() already sent the
+        buckets (GradientOverlap); only the flag check / correction and the step kernel are left.  opt: the
+        OptimizerConfig whose name picks the kernel (None or `sgd`: rn_optim_sgd_step with lr, momentum, nesterov; the
+        others: rn_optim_step, lr being the rule's scalar — for Adam alpha_t)."""
         lib, st = self.lib, _C.current_stream()
         unscale = 1.0 / self.loss_scale["scale"] if self.loss_scale else 1.0
-        def sgd(skip_ptr):
-            _C.check(lib.rn_optim_sgd_step(self.P.data_ptr(), self.G.data_ptr(), self.V.data_ptr(),
-                                           self.E.data_ptr() if ema_decay is not None else None, self.Pbf.data_ptr(),
-                                           self.segs_dev.data_ptr(), self.block_seg_dev.data_ptr(), self.n_blocks,
-                                           lr, momentum, ema_decay if ema_decay is not None else 0.0, 1 if nesterov else 0,
-                                           skip_ptr, st), "rn_optim_sgd_step")
+        if opt is not None and opt.name != self._slot_owner:
+            raise RuntimeError(f"optimizer_step: the slot arenas belong to {self._slot_owner}, not {opt.name}")
+        if opt is not None and opt.name != "sgd":
+            rule = self._optim_rule(opt, lr, ema_decay)
+            def sgd(skip_ptr):
+                _C.check(lib.rn_optim_step(self.P.data_ptr(), self.G.data_ptr(), self.V.data_ptr(), _C.ptr(self.S1),
+                                           _C.ptr(self.S2), self.E.data_ptr() if ema_decay is not None else None,
+                                           self.Pbf.data_ptr(), self.segs_dev.data_ptr(), self.block_seg_dev.data_ptr(),
+                                           self.n_blocks, ctypes.byref(rule), skip_ptr, st), "rn_optim_step")
+        else:
+            def sgd(skip_ptr):
+                _C.check(lib.rn_optim_sgd_step(self.P.data_ptr(), self.G.data_ptr(), self.V.data_ptr(),
+                                               self.E.data_ptr() if ema_decay is not None else None, self.Pbf.data_ptr(),
+                                               self.segs_dev.data_ptr(), self.block_seg_dev.data_ptr(), self.n_blocks,
+                                               lr, momentum, ema_decay if ema_decay is not None else 0.0,
+                                               1 if nesterov else 0, skip_ptr, st), "rn_optim_sgd_step")
         if overlapped:
             # G[0] = sum over the ranks of "a clip factor != 1 or the gradient norm is not finite".  A NaN norm leaves every
             # factor at 1 (fmaxf drops it): rn_optim_clip_factors tests the global norm for finiteness on its own and
@@ -1894,6 +1970,7 @@ class TrainEngine:
             self.loss_scale = dict(scale=float(opt.initial_loss_scale), good=0, growth_steps=int(opt.loss_scale_growth_steps),
                                    skipped=False)
         with torch.cuda.device(self.dev):
+            self._bind_optimizer()          # slot arenas of the rule `opt` names (a no-op unless the optimizer was replaced)
             alpha = cfg.weight_decay_alpha if cfg.use_weight_decay else 0.0
             self._prepack_dgrad_weights()
             self.small.begin_step(targets["num-positives"])
@@ -1914,9 +1991,11 @@ class TrainEngine:
             overlapped = self.overlap.on      # backward() sent the gradient buckets as it completed them
             if overlapped and self.overlap.done != len(self.overlap.buckets):
                 raise RuntimeError("overlapped all-reduce: not every gradient bucket was launched")
-            self.optimizer_step(opt.lr(step), opt.momentum, opt.clipnorm, alpha,
+            # step_size: the schedule's rate; Adam's alpha_t with t = step + 1 — `step` was read after
+            # _resolve_loss_scale(), so a dropped mixed_float16 step does not advance t
+            self.optimizer_step(opt.step_size(step), opt.momentum, opt.clipnorm, alpha,
                                 opt.ema_decay(step) if opt.use_moving_average else None, nesterov=opt.nesterov,
-                                overlapped=overlapped)
+                                overlapped=overlapped, opt=opt)
             self.syncbn_messages_per_step = self.small.end_step()
             self.step_count += 1              # (taken back by _resolve_loss_scale when the step turns out dropped)
             opt.iterations = self.step_count
