@@ -644,9 +644,7 @@ int rn_balance_features_bwd(void* const* dout, void* const* in, void* const* din
  *                      last bucket's all-reduce); if some rank's clip fired, `apply` with correction != NULL writes
  *                      (factor - 1) * g, which is all-reduced and added — the sum then equals the reference's
  *                      clip-then-all-reduce order (executor.py:432-437).
- *   rn_optim_sgd_step  v = m v - lr g; w += v (or w += m v - lr g with the new v: nesterov); ema -= (1-d)(ema - w);
- *                      bf16 copy of w.  skip_flag (device f32, may be NULL): non-zero = drop the step
- *                      (LossScaleOptimizer.apply_gradients with non-finite gradients).
+ *   rn_optim_step      the update rule, the moving average and the 16-bit copy of w: the contract further down.
  */
 int rn_optim_chunk(void);
 size_t rn_optim_workspace_bytes(int num_blocks, int num_segments);
@@ -661,18 +659,19 @@ int rn_optim_clip_factors(const void* segs_dev, int num_segments, int num_blocks
                           float* metrics, float* flags, void* workspace, size_t workspace_bytes, void* stream);
 int rn_optim_clip_apply(float* grads, float* correction, const void* segs_dev, const int32_t* block_seg_dev,
                         int num_blocks, void* workspace, size_t workspace_bytes, void* stream);
-int rn_optim_sgd_step(float* params, const float* grads, float* momentum_buf, float* ema, void* params_bf16,
-                      const void* segs_dev, const int32_t* block_seg_dev, int num_blocks, float lr, float momentum,
-                      float ema_decay, int nesterov, const float* skip_flag, void* stream);
 
 /*
- * Adam, RMSprop and Adagrad of Keras optimizer_v2 (TF 2.8) over the same arenas, segment table and blocks as
- * rn_optim_sgd_step, with the same access rules: 16 bytes per lane and array where the fp32 offset and the 16-bit offset
- * of a block are multiples of 4, a scalar tail, a scalar loop for other offsets; nothing outside tensor elements is
- * written; skip_flag (device f32, may be NULL) non-zero = no array changes; ema == NULL = no moving average; the 16-bit
- * copy is the cast of the kernel's own new fp32 weight.  Every line below is evaluated in fp32 in the order written,
- * each product, sum, root and quotient rounded once; 1 - beta1, 1 - beta2, 1 - rho and 1 - ema_decay are fp32
- * differences formed on the device.
+ * The parameter update: SGD, Adam, RMSprop and Adagrad of Keras optimizer_v2 (TF 2.8) over the arenas, segment table and
+ * blocks above, one kernel.  Access rules: 16 bytes per lane and array where the fp32 offset and the 16-bit offset of a
+ * block are multiples of 4, a scalar tail, a scalar loop for other offsets; nothing outside tensor elements is written;
+ * skip_flag (device f32, may be NULL) non-zero = no array changes (LossScaleOptimizer.apply_gradients with non-finite
+ * gradients); ema == NULL = no moving average; the 16-bit copy is the cast of the kernel's own new fp32 weight.  Every
+ * line below is evaluated in fp32 in the order written, each product, sum, root and quotient rounded once; 1 - beta1,
+ * 1 - beta2, 1 - rho and 1 - ema_decay are fp32 differences formed on the device.
+ *   RN_OPT_SGD       slot0 = momentum (read and written also when rule.momentum == 0)
+ *       v  = momentum * v - lr * g
+ *       w  = w + v                         without RN_OPT_NESTEROV
+ *       w  = w + (momentum * v - lr * g)   with RN_OPT_NESTEROV, v the new velocity
  *   RN_OPT_ADAM      slot0 = m, slot1 = v, slot2 = vhat (RN_OPT_AMSGRAD only)
  *       m  = m + (g - m) * (1 - beta1)
  *       v  = v + (g * g - v) * (1 - beta2)
@@ -693,9 +692,10 @@ int rn_optim_sgd_step(float* params, const float* grads, float* momentum_buf, fl
  *   all rules, ema != NULL:  ema = ema - (1 - ema_decay) * (ema - w), w the new weight
  * A slot the rule does not use is neither read nor written and may be NULL.  RN_EINVAL before any launch: an unknown
  * rule, a flag that does not belong to the rule, a missing slot array the rule needs.
+ * rn_optim_sgd_step is the RN_OPT_SGD rule with scalar arguments (nesterov != 0: RN_OPT_NESTEROV).
  */
-enum { RN_OPT_ADAM = 1, RN_OPT_RMSPROP = 2, RN_OPT_ADAGRAD = 3 };
-enum { RN_OPT_AMSGRAD = 1, RN_OPT_CENTERED = 2, RN_OPT_MOMENTUM = 4 };
+enum { RN_OPT_ADAM = 1, RN_OPT_RMSPROP = 2, RN_OPT_ADAGRAD = 3, RN_OPT_SGD = 4 };
+enum { RN_OPT_AMSGRAD = 1, RN_OPT_CENTERED = 2, RN_OPT_MOMENTUM = 4, RN_OPT_NESTEROV = 8 };
 typedef struct {
   int32_t rule, flags;
   float lr, beta1, beta2, rho, momentum, epsilon, ema_decay;
@@ -703,6 +703,9 @@ typedef struct {
 int rn_optim_step(float* params, const float* grads, float* slot0, float* slot1, float* slot2, float* ema,
                   void* params_bf16, const void* segs_dev, const int32_t* block_seg_dev, int num_blocks,
                   const rn_optim_rule* rule /* host */, const float* skip_flag, void* stream);
+int rn_optim_sgd_step(float* params, const float* grads, float* momentum_buf, float* ema, void* params_bf16,
+                      const void* segs_dev, const int32_t* block_seg_dev, int num_blocks, float lr, float momentum,
+                      float ema_decay, int nesterov, const float* skip_flag, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * C1-C3  collectives of the data-parallel step over RCCL / xGMI (the reference reaches them through

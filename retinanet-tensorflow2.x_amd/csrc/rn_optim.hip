@@ -7,10 +7,10 @@
 //   stage 2  per-tensor norm -> clip_by_norm factor, global norm of the clipped tensors ->
 //            clip_by_global_norm factor (executor.py:401-407; tf semantics c/max(norm,c));
 //   stage 3  g <- g * factor[tensor]                      (then the data-parallel all-reduce SUM)
-//   stage 4  Keras SGD momentum  v <- m v - lr g ; w <- w + v   (optimizers/builder.py:45)
+//   stage 4  the update rule training.optimizer.name picks (optimizers/builder.py:45): Keras SGD momentum
+//            v <- m v - lr g ; w <- w + v, or Adam / RMSprop / Adagrad — one kernel template, rn_optim_step
 //            tfa MovingAverage   ema <- ema - (1-d)(ema - w)    (optimizers/builder.py:51-54)
 //            and the bf16 compute copy of w for the next forward.
-//            training.optimizer.name = adam | rmsprop | adagrad: the Keras rule instead of SGD (rn_optim_step)
 // Deterministic: block partials are added in index order.  HBM-bound: 34.4 M params.
 #include "rn_common.h"
 
@@ -163,71 +163,6 @@ optim_scale_kernel(float* g, float* out, const OptSeg* __restrict__ segs,
   }
 }
 
-__global__ void __launch_bounds__(OPT_THREADS)
-optim_sgd_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v, float* __restrict__ ema,
-                 uint16_t* __restrict__ wbf16, const OptSeg* __restrict__ segs, const int* __restrict__ block_seg,
-                 float lr, float momentum, float ema_decay, int use_ema, int nesterov,
-                 const float* __restrict__ skip_flag) {
-  // LossScaleOptimizer.apply_gradients: a step whose gradients are not finite on ANY replica is dropped
-  if (skip_flag && skip_flag[0] != 0.0f) return;
-  const int si = block_seg[blockIdx.x];
-  const OptSeg s = segs[si];
-  const long long b0 = (long long)(blockIdx.x - s.block_begin) * OPT_CHUNK;
-  long long b1 = b0 + OPT_CHUNK;
-  if (b1 > s.size) b1 = s.size;
-#define SGD_ELEM(w_, g_, v_, e_)                                                                       \
-  do {                                                                                                 \
-    const float vel__ = momentum * (v_) - lr * (g_);                                                   \
-    /* Keras SGD: w += v  (momentum), or w += momentum * v - lr * g with the NEW v (nesterov=True) */   \
-    const float nw__ = (w_) + (nesterov ? momentum * vel__ - lr * (g_) : vel__);                       \
-    (v_) = vel__;                                                                                      \
-    (w_) = nw__;                                                                                       \
-    if (use_ema) (e_) = (e_) - (1.0f - ema_decay) * ((e_) - nw__);                                     \
-  } while (0)
-  const bool vec = ((s.offset + b0) & 3) == 0 && (s.bf16_offset < 0 || ((s.bf16_offset + b0) & 3) == 0);
-  if (vec) {   // 16 bytes per lane and array; scalar tail
-    const long long base = s.offset + b0;
-    const int n = (int)(b1 - b0), n4 = n >> 2;
-    float4* w4 = (float4*)(w + base);
-    const float4* g4 = (const float4*)(g + base);
-    float4* v4 = (float4*)(v + base);
-    float4* e4 = use_ema ? (float4*)(ema + base) : nullptr;
-    uint2* h4 = s.bf16_offset >= 0 ? (uint2*)(wbf16 + s.bf16_offset + b0) : nullptr;
-    for (int i = threadIdx.x; i < n4; i += OPT_THREADS) {
-      float4 wv = w4[i], vv = v4[i], ev = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      const float4 gv = g4[i];
-      if (use_ema) ev = e4[i];
-      SGD_ELEM(wv.x, gv.x, vv.x, ev.x); SGD_ELEM(wv.y, gv.y, vv.y, ev.y);
-      SGD_ELEM(wv.z, gv.z, vv.z, ev.z); SGD_ELEM(wv.w, gv.w, vv.w, ev.w);
-      v4[i] = vv;
-      w4[i] = wv;
-      if (use_ema) e4[i] = ev;
-      if (h4) h4[i] = make_uint2((unsigned)rn_f32_to_bf16(wv.x) | ((unsigned)rn_f32_to_bf16(wv.y) << 16),
-                                 (unsigned)rn_f32_to_bf16(wv.z) | ((unsigned)rn_f32_to_bf16(wv.w) << 16));
-    }
-    if ((int)threadIdx.x < (n & 3)) {
-      const long long i = b0 + 4 * n4 + threadIdx.x, o = s.offset + i;
-      float wv = w[o], vv = v[o], ev = use_ema ? ema[o] : 0.0f;
-      SGD_ELEM(wv, g[o], vv, ev);
-      v[o] = vv;
-      w[o] = wv;
-      if (use_ema) ema[o] = ev;
-      if (s.bf16_offset >= 0) wbf16[s.bf16_offset + i] = rn_f32_to_bf16(wv);
-    }
-  } else {
-    for (long long i = b0 + threadIdx.x; i < b1; i += OPT_THREADS) {
-      const long long o = s.offset + i;
-      float wv = w[o], vv = v[o], ev = use_ema ? ema[o] : 0.0f;
-      SGD_ELEM(wv, g[o], vv, ev);
-      v[o] = vv;
-      w[o] = wv;
-      if (use_ema) ema[o] = ev;
-      if (s.bf16_offset >= 0) wbf16[s.bf16_offset + i] = rn_f32_to_bf16(wv);
-    }
-  }
-#undef SGD_ELEM
-}
-
 extern "C" size_t rn_optim_workspace_bytes(int num_blocks, int num_segments) {
   return 2 * rn_align_up((size_t)num_blocks * sizeof(double), 256) + rn_align_up((size_t)num_segments * sizeof(float), 256) + 256;
 }
@@ -307,24 +242,11 @@ extern "C" int rn_optim_clip(float* grads, const float* params, const void* segs
   return rn_optim_clip_apply(grads, nullptr, segs_dev, block_seg_dev, num_blocks, workspace, workspace_bytes, stream);
 }
 
-extern "C" int rn_optim_sgd_step(float* params, const float* grads, float* momentum_buf, float* ema,
-                                 void* params_bf16, const void* segs_dev, const int32_t* block_seg_dev,
-                                 int num_blocks, float lr, float momentum, float ema_decay, int nesterov,
-                                 const float* skip_flag, void* stream) {
-  RN_CHECK_ARG(params && grads && momentum_buf && segs_dev && block_seg_dev && num_blocks > 0,
-               "rn_optim_sgd_step: bad argument");
-  hipLaunchKernelGGL(optim_sgd_kernel, dim3(num_blocks), dim3(OPT_THREADS), 0, (hipStream_t)stream, params, grads,
-                     momentum_buf, ema, (uint16_t*)params_bf16, (const OptSeg*)segs_dev, block_seg_dev, lr, momentum,
-                     ema_decay, ema ? 1 : 0, nesterov, skip_flag);
-  RN_CHECK_LAUNCH();
-  return RN_OK;
-}
-
-// ---- Adam / RMSprop / Adagrad (Keras optimizer_v2; the contract with its op order is in include/rnet_hip.h) ----------
-// The same walk as optim_sgd_kernel: one block per OPT_CHUNK elements of one tensor, 16 bytes per lane and array where
-// the fp32 and the 16-bit offset allow it, a scalar tail, a scalar loop for every other offset.  The rule, its flags and
-// the moving average are template parameters: the element loop has no branch on them, and a slot the rule does not use
-// is neither read nor written (its pointer may be NULL).
+// ---- SGD / Adam / RMSprop / Adagrad (Keras optimizer_v2; the contract with its op order is in include/rnet_hip.h) ----
+// One block per OPT_CHUNK elements of one tensor, 16 bytes per lane and array where the fp32 and the 16-bit offset
+// allow it, a scalar tail, a scalar loop for every other offset.  The rule, its flags and the moving average are
+// template parameters: the element loop has no branch on them, and a slot the rule does not use is neither read nor
+// written (its pointer may be NULL).
 struct OptK { float lr, c1, c2, momentum, eps, omd; };   // c1 = 1 - beta1 | 1 - rho, c2 = 1 - beta2, omd = 1 - ema_decay
 
 template <int RULE, int FLAGS>
@@ -366,10 +288,15 @@ __device__ __forceinline__ void optim_rule_elem(float& w, const float g, float& 
     } else {                                          // Keras' own formula: epsilon outside the root
       nw = w - (k.lr * g) / (sqrtf(den) + k.eps);
     }
-  } else {
+  } else if constexpr (RULE == RN_OPT_ADAGRAD) {
     const float acc = s0 + g * g;
     s0 = acc;
     nw = w - (k.lr * g) / (sqrtf(acc) + k.eps);
+  } else {   // Keras SGD: w += v, or w += momentum * v - lr * g with the NEW v (nesterov=True)
+    const float vel = k.momentum * s0 - k.lr * g;
+    s0 = vel;
+    if constexpr ((FLAGS & RN_OPT_NESTEROV) != 0) nw = w + (k.momentum * vel - k.lr * g);
+    else nw = w + vel;
   }
   w = nw;
   if constexpr (EMA) e = e - k.omd * (e - nw);
@@ -451,7 +378,8 @@ extern "C" int rn_optim_step(float* params, const float* grads, float* slot0, fl
   RN_CHECK_ARG(params && grads && segs_dev && block_seg_dev && num_blocks > 0 && rule, "rn_optim_step: bad argument");
   const int allowed = rule->rule == RN_OPT_ADAM ? RN_OPT_AMSGRAD
                       : rule->rule == RN_OPT_RMSPROP ? (RN_OPT_CENTERED | RN_OPT_MOMENTUM)
-                      : rule->rule == RN_OPT_ADAGRAD ? 0 : -1;
+                      : rule->rule == RN_OPT_ADAGRAD ? 0
+                      : rule->rule == RN_OPT_SGD ? RN_OPT_NESTEROV : -1;
   RN_CHECK_ARG(allowed >= 0, "rn_optim_step: unknown rule %d", rule->rule);
   RN_CHECK_ARG((rule->flags & ~allowed) == 0, "rn_optim_step: rule %d does not take flags 0x%x", rule->rule, rule->flags);
   const bool need1 = rule->rule == RN_OPT_ADAM || (rule->flags & RN_OPT_MOMENTUM);
@@ -480,12 +408,32 @@ extern "C" int rn_optim_step(float* params, const float* grads, float* slot0, fl
       case RN_OPT_MOMENTUM: OPT_LAUNCH(RN_OPT_RMSPROP, RN_OPT_MOMENTUM); break;
       default: OPT_LAUNCH(RN_OPT_RMSPROP, RN_OPT_CENTERED | RN_OPT_MOMENTUM); break;
     }
-  } else {
+  } else if (rule->rule == RN_OPT_ADAGRAD) {
     OPT_LAUNCH(RN_OPT_ADAGRAD, 0);
+  } else {
+    if (rule->flags & RN_OPT_NESTEROV) OPT_LAUNCH(RN_OPT_SGD, RN_OPT_NESTEROV);
+    else OPT_LAUNCH(RN_OPT_SGD, 0);
   }
 #undef OPT_LAUNCH
   RN_CHECK_LAUNCH();
   return RN_OK;
+}
+
+// the SGD rule with scalar arguments
+extern "C" int rn_optim_sgd_step(float* params, const float* grads, float* momentum_buf, float* ema,
+                                 void* params_bf16, const void* segs_dev, const int32_t* block_seg_dev,
+                                 int num_blocks, float lr, float momentum, float ema_decay, int nesterov,
+                                 const float* skip_flag, void* stream) {
+  RN_CHECK_ARG(params && grads && momentum_buf && segs_dev && block_seg_dev && num_blocks > 0,
+               "rn_optim_sgd_step: bad argument");
+  rn_optim_rule r = {};
+  r.rule = RN_OPT_SGD;
+  r.flags = nesterov ? RN_OPT_NESTEROV : 0;
+  r.lr = lr;
+  r.momentum = momentum;
+  r.ema_decay = ema_decay;
+  return rn_optim_step(params, grads, momentum_buf, nullptr, nullptr, ema, params_bf16, segs_dev, block_seg_dev,
+                       num_blocks, &r, skip_flag, stream);
 }
 
 // ---- dgrad weight transform: master f32 [Cout][R][S][Cin] -> bf16 [Cin_pad][R][S][Cout], taps

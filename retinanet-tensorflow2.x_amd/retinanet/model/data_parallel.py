@@ -260,14 +260,14 @@ class GradientOverlap:
                 self._works.append(dist.all_reduce(self.G[bkt["begin"]:bkt["end"]], group=self.pg_c1, async_op=True))
                 self.bucket_host_ms = max(self.bucket_host_ms, (time.perf_counter() - t0) * 1e3)
 
-    def finish(self, optimistic_sgd, read_flag=True):
+    def finish(self, optimistic_update, read_flag=True):
         """After the join: wait for the buckets; when some rank's clip fired, all-reduce the correction.
-        optimistic_sgd: callable that enqueues the SGD kernel with the device-side predicate "G[0] == 0" (no clip fired on
+        optimistic_update: callable that enqueues the step kernel with the device-side predicate "G[0] == 0" (no clip fired on
         any rank, no gradient non-finite: the common case).  The flag goes to pinned host memory with an asynchronous copy
         enqueued BEFORE that kernel, the host waits for the copy's event only — the kernel runs while the host decides and
         carries on enqueueing (a blocking `.item()` left the device idle for the host's wake-up and the next launches:
         0.24 - 0.38 ms per step, bench.py's extra.dp_overhead).  Returns True when the optimistic kernel applied the step;
-        False when the flag fired (the kernel was a no-op: the caller runs the SGD kernel after the correction below).
+        False when the flag fired (the kernel was a no-op: the caller runs the step kernel after the correction below).
         read_flag=False (bench.py's extra.dp_overhead ONLY: what the host read costs): no read, no kernel, "not fired"."""
         cur = torch.cuda.current_stream(self.dev)
         for w in self._works:
@@ -278,7 +278,7 @@ class GradientOverlap:
         if read_flag:
             self._flag_host.copy_(self.G[0:1], non_blocking=True)
             self._flag_event.record(cur)
-            optimistic_sgd()                         # predicate on the device: a no-op when G[0] != 0
+            optimistic_update()                      # predicate on the device: a no-op when G[0] != 0
             self._flag_event.synchronize()
             fired = float(self._flag_host[0]) != 0.0
             applied = not fired

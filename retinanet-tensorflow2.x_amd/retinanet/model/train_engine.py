@@ -1857,9 +1857,12 @@ class TrainEngine:
         self.overlap.native_comm = comm
 
     def _optim_rule(self, opt, lr, ema_decay):
-        """rn_optim_rule of an Adam / RMSprop / Adagrad configuration; lr is the kernel's scalar (OptimizerConfig.step_size)"""
-        rule = {"adam": _C.RN_OPT_ADAM, "rmsprop": _C.RN_OPT_RMSPROP, "adagrad": _C.RN_OPT_ADAGRAD}[opt.name]
+        """rn_optim_rule of an optimizer configuration; lr is the kernel's scalar (OptimizerConfig.step_size)"""
+        rule = {"sgd": _C.RN_OPT_SGD, "adam": _C.RN_OPT_ADAM, "rmsprop": _C.RN_OPT_RMSPROP,
+                "adagrad": _C.RN_OPT_ADAGRAD}[opt.name]
         flags = 0
+        if opt.name == "sgd" and opt.nesterov:
+            flags |= _C.RN_OPT_NESTEROV
         if opt.name == "adam" and opt.amsgrad:
             flags |= _C.RN_OPT_AMSGRAD
         if opt.name == "rmsprop":
@@ -1872,31 +1875,28 @@ class TrainEngine:
         """weight decay + per-tensor / global clipping (executor.py:401-407) + all-reduce SUM (executor.py:436-437)
         + the update rule / moving average (optimizers/builder.py:45-54).  overlapped=True: backward() already sent the
         buckets (GradientOverlap); only the flag check / correction and the step kernel are left.  opt: the
-        OptimizerConfig whose name picks the kernel (None or `sgd`: rn_optim_sgd_step with lr, momentum, nesterov; the
-        others: rn_optim_step, lr being the rule's scalar — for Adam alpha_t)."""
+        OptimizerConfig whose name picks the rule of rn_optim_step, lr being the rule's scalar (for Adam alpha_t); None:
+        the SGD rule of lr, momentum, nesterov."""
         lib, st = self.lib, _C.current_stream()
         unscale = 1.0 / self.loss_scale["scale"] if self.loss_scale else 1.0
         if opt is not None and opt.name != self._slot_owner:
             raise RuntimeError(f"optimizer_step: the slot arenas belong to {self._slot_owner}, not {opt.name}")
-        if opt is not None and opt.name != "sgd":
+        if opt is not None:
             rule = self._optim_rule(opt, lr, ema_decay)
-            def sgd(skip_ptr):
-                _C.check(lib.rn_optim_step(self.P.data_ptr(), self.G.data_ptr(), self.V.data_ptr(), _C.ptr(self.S1),
-                                           _C.ptr(self.S2), self.E.data_ptr() if ema_decay is not None else None,
-                                           self.Pbf.data_ptr(), self.segs_dev.data_ptr(), self.block_seg_dev.data_ptr(),
-                                           self.n_blocks, ctypes.byref(rule), skip_ptr, st), "rn_optim_step")
         else:
-            def sgd(skip_ptr):
-                _C.check(lib.rn_optim_sgd_step(self.P.data_ptr(), self.G.data_ptr(), self.V.data_ptr(),
-                                               self.E.data_ptr() if ema_decay is not None else None, self.Pbf.data_ptr(),
-                                               self.segs_dev.data_ptr(), self.block_seg_dev.data_ptr(), self.n_blocks,
-                                               lr, momentum, ema_decay if ema_decay is not None else 0.0,
-                                               1 if nesterov else 0, skip_ptr, st), "rn_optim_sgd_step")
+            rule = _C.OptimRule(rule=_C.RN_OPT_SGD, flags=_C.RN_OPT_NESTEROV if nesterov else 0, lr=lr, momentum=momentum,
+                                ema_decay=ema_decay if ema_decay is not None else 0.0)
+
+        def update(skip_ptr):
+            _C.check(lib.rn_optim_step(self.P.data_ptr(), self.G.data_ptr(), self.V.data_ptr(), _C.ptr(self.S1),
+                                       _C.ptr(self.S2), self.E.data_ptr() if ema_decay is not None else None,
+                                       self.Pbf.data_ptr(), self.segs_dev.data_ptr(), self.block_seg_dev.data_ptr(),
+                                       self.n_blocks, ctypes.byref(rule), skip_ptr, st), "rn_optim_step")
         if overlapped:
             # G[0] = sum over the ranks of "a clip factor != 1 or the gradient norm is not finite".  A NaN norm leaves every
             # factor at 1 (fmaxf drops it): rn_optim_clip_factors tests the global norm for finiteness on its own and
             # sets flags[0] then too, so G[0] == 0 also says every gradient is finite
-            applied = self.overlap.finish(lambda: sgd(self.G.data_ptr()), read_flag=not self.price_without_flag_read)
+            applied = self.overlap.finish(lambda: update(self.G.data_ptr()), read_flag=not self.price_without_flag_read)
             if applied:
                 self.refresh_packs()
                 if self.loss_scale:
@@ -1915,7 +1915,7 @@ class TrainEngine:
             if self.dp_active:
                 from retinanet.distribute import all_reduce_sum_bucketed
                 all_reduce_sum_bucketed(self.G, 2 if self.world == 1 else self.world, self.pg)   # executor.py:436-437: SUM after clipping
-        sgd(skip)
+        update(skip)
         self.refresh_packs()
         if self.loss_scale:
             self._update_loss_scale()
@@ -1924,7 +1924,7 @@ class TrainEngine:
         """tf.keras.mixed_precision.LossScaleOptimizer(dynamic=True) (optimizers/builder.py:56-64): halve the scale
         when a step's gradients were not finite (the step was dropped), double it after `growth_steps` good steps.
 
-        The SGD kernel drops the update itself (skip pointer); what the HOST needs — the next loss scale, whether
+        The step kernel drops the update itself (skip pointer); what the HOST needs — the next loss scale, whether
         optimizer.iterations advances — it needs only when the NEXT step reaches its loss: the flag goes to pinned
         memory with an asynchronous copy here and is applied by _resolve_loss_scale(), which the next train_step calls
         after it has enqueued its forward pass (or finish_step(), for whoever reads the counters in between).  Reading

@@ -367,6 +367,31 @@ def sgd(lay, w, g, v, ema, lr, m, d, nesterov):
     return w1, v1, e1
 
 
+def emu_sgd(lay, w, g, v, e, pbf, lr, m, d, nesterov, fault=None):
+    """The SGD rule in NumPy float32, the header's op order with one rounding per operation: what the kernel must produce
+    bit for bit (test_gpu_optimizer.py) and what the acceptance rule must accept (test_optim_ref_cpu.py).  CPU arenas in,
+    new (w, v, e, 16-bit copy) out; `fault` plants one single fault the rule must reject."""
+    F32 = np.float32
+    w, g, v, e = w.numpy().copy(), g.numpy(), v.numpy().copy(), e.numpy().copy()
+    pbf = pbf.clone()
+    lr, m, d = F32(lr), F32(m), F32(d)
+    for s in lay.segs:
+        o, n = int(s["offset"]), int(s["size"])
+        sl = slice(o, o + n)
+        vel = m * v[sl] - lr * g[sl]
+        old = v[sl] if fault == "nesterov_old_v" else vel
+        nw = w[sl] + ((m * old - lr * g[sl]) if nesterov else vel)
+        v[sl], w[sl] = vel, nw
+        k = d if fault == "ema_swapped" else F32(1.0) - d
+        e[sl] = e[sl] - k * (e[sl] - nw)
+        if s["bf"] >= 0:
+            x = torch.from_numpy(nw.copy())
+            if fault == "copy_truncates":
+                x = (x.view(torch.int32) & -65536).view(torch.float32)
+            pbf[int(s["bf"]):int(s["bf"]) + n] = x.to(pbf.dtype)
+    return torch.from_numpy(w), torch.from_numpy(v), torch.from_numpy(e), pbf
+
+
 # ---- the rule -----------------------------------------------------------------------------------------------------------
 def ratio(got, ref):
     """largest |got - ref| / bound over the packed elements; a bound of 0 asks for equality (ratio 0 or inf)"""

@@ -1,5 +1,5 @@
-"""Float64 reference of rn_optim_step (Adam, RMSprop, Adagrad of Keras optimizer_v2; the contract is the comment above
-rn_optim_step in include/rnet_hip.h), the inputs of its tests and the rule that compares the kernel with the reference.
+"""Float64 reference of rn_optim_step (SGD, Adam, RMSprop, Adagrad of Keras optimizer_v2; the contract is the comment
+above rn_optim_step in include/rnet_hip.h), the inputs of its tests and the rule that compares the kernel with the reference.
 The arenas and their layout are optim_ref's (`Layout`, `pack`, sentinels); nothing there is changed.
 
 The reference
@@ -10,6 +10,7 @@ One function, `step`, evaluates the header's lines on float64 tensors, in the he
             momentum:  mom' = momentum mom + (lr g) / sqrt(d + eps);  w' = w - mom'
             plain:     w' = w - (lr g) / (sqrt(d) + eps)
   adagrad   acc' = acc + g g;  w' = w - (lr g) / (sqrt(acc') + eps)
+  sgd       v' = momentum v - lr g;  w' = w + v'   or, nesterov,  w' = w + (momentum v' - lr g)
   all       e' = e - omd (e - w')
 Every scalar the kernel receives as a C float enters as its float32 value; c1 = 1 - beta1 (or 1 - rho), c2 = 1 - beta2 and
 omd = 1 - ema_decay are the float32 differences, as the kernel forms them (`f32_consts=False` takes the exact differences
@@ -51,8 +52,8 @@ from pyramid_ref import F64, Ref
 
 U = 2.0 ** -24
 TINY = 2.0 ** -149
-ADAM, RMSPROP, ADAGRAD = 1, 2, 3
-AMSGRAD, CENTERED, MOMENTUM = 1, 2, 4
+ADAM, RMSPROP, ADAGRAD, SGD = 1, 2, 3, 4
+AMSGRAD, CENTERED, MOMENTUM, NESTEROV = 1, 2, 4, 8
 F32 = np.float32
 
 
@@ -76,7 +77,7 @@ class Rule(NamedTuple):
 
 MODES = {"adam": (ADAM, 0), "adam+amsgrad": (ADAM, AMSGRAD), "rmsprop": (RMSPROP, 0), "rmsprop+momentum": (RMSPROP, MOMENTUM),
          "rmsprop+centered": (RMSPROP, CENTERED), "rmsprop+centered+momentum": (RMSPROP, CENTERED | MOMENTUM),
-         "adagrad": (ADAGRAD, 0)}
+         "adagrad": (ADAGRAD, 0), "sgd": (SGD, 0), "sgd+nesterov": (SGD, NESTEROV)}
 BETA1, BETA2, RHO, MOM, EPS, LR, DECAY, ACC0 = 0.9, 0.999, 0.9, 0.9, 1e-7, 0.01, 0.9998, 0.1
 
 
@@ -89,7 +90,7 @@ def mode_rule(mode, t=1, ema=True, lr=LR):
     """the rule of `mode` at step t (1-based), hyper-parameters of Keras' defaults with momentum 0.9 where the mode has one"""
     rule, flags = MODES[mode]
     step = adam_alpha(lr, BETA1, BETA2, t) if rule == ADAM else lr
-    return Rule(rule, flags, O.f32(step), O.f32(BETA1), O.f32(BETA2), O.f32(RHO), O.f32(MOM if flags & MOMENTUM else 0.0),
+    return Rule(rule, flags, O.f32(step), O.f32(BETA1), O.f32(BETA2), O.f32(RHO), O.f32(MOM if flags & MOMENTUM or rule == SGD else 0.0),
                 O.f32(EPS), O.f32(DECAY if ema else 0.0))
 
 
@@ -189,6 +190,10 @@ def step(r, w, g, s0, s1=None, s2=None, ema=None, f32_consts=True):
         acc = s0 + g * g
         out["s0"] = acc
         nw = w - (g * r.lr) / acc.sqrt().add_scalar(r.epsilon)
+    elif r.rule == SGD:
+        vel = s0 * r.momentum - g * r.lr
+        out["s0"] = vel
+        nw = w + (vel * r.momentum - g * r.lr) if r.flags & NESTEROV else w + vel
     else:
         raise ValueError(r.rule)
     out["w"] = nw
@@ -282,8 +287,8 @@ def engine_layout(eng, sample=True):
 
 def engine_rule(opt, step):
     """the Rule a TrainEngine hands the kernel at optimizer step `step` (0-based: optimizer.iterations before the step)"""
-    rule = {"adam": ADAM, "rmsprop": RMSPROP, "adagrad": ADAGRAD}[opt.name]
-    flags = (AMSGRAD if opt.name == "adam" and opt.amsgrad else 0)
+    rule = {"adam": ADAM, "rmsprop": RMSPROP, "adagrad": ADAGRAD, "sgd": SGD}[opt.name]
+    flags = (AMSGRAD if opt.name == "adam" and opt.amsgrad else 0) | (NESTEROV if opt.name == "sgd" and opt.nesterov else 0)
     if opt.name == "rmsprop":
         flags = (CENTERED if opt.centered else 0) | (MOMENTUM if opt.momentum > 0 else 0)
     lr = opt.lr(step)

@@ -1,4 +1,4 @@
-"""rn_optim_step (Adam, RMSprop, Adagrad) against the float64 reference of optim_rules_ref.py: every mode for three
+"""rn_optim_step (SGD, Adam, RMSprop, Adagrad) against the float64 reference of optim_rules_ref.py: every mode for three
 consecutive steps on the engine's offsets and on offsets it never produces, both builds, the skip flag, the refusals, and
 the same rule on a TrainEngine's own arenas after real training steps, through a checkpoint, over ten Adam steps and
 through the overlapped data-parallel step on one rank of an RCCL group.  The
@@ -110,14 +110,17 @@ def test_skip_flag_leaves_every_arena_alone(cuda, layouts, mode, build):
 
 
 # ---- 3. refusals: RN_EINVAL, nothing launched --------------------------------------------------------------------------------
-BAD = {"rule 0": (dict(rule=0), ()), "rule 4": (dict(rule=4), ()), "rule -1": (dict(rule=-1), ()),
+BAD = {"rule 0": (dict(rule=0), ()), "rule 5": (dict(rule=5), ()), "rule -1": (dict(rule=-1), ()),
        "adam + centered": (dict(rule=R.ADAM, flags=R.CENTERED), ()), "adam + momentum": (dict(rule=R.ADAM, flags=R.MOMENTUM), ()),
        "rmsprop + amsgrad": (dict(rule=R.RMSPROP, flags=R.AMSGRAD), ()), "adagrad + amsgrad": (dict(rule=R.ADAGRAD, flags=R.AMSGRAD), ()),
        "adagrad + centered": (dict(rule=R.ADAGRAD, flags=R.CENTERED), ()), "flag 8": (dict(rule=R.ADAM, flags=8), ()),
        "no slot0": (dict(rule=R.ADAGRAD), ("s0",)), "adam without v": (dict(rule=R.ADAM), ("s1",)),
        "amsgrad without vhat": (dict(rule=R.ADAM, flags=R.AMSGRAD), ("s2",)),
        "momentum without its slot": (dict(rule=R.RMSPROP, flags=R.MOMENTUM), ("s1",)),
-       "centered without mg": (dict(rule=R.RMSPROP, flags=R.CENTERED), ("s2",)), "no blocks": (dict(rule=R.ADAM), ("blocks",))}
+       "centered without mg": (dict(rule=R.RMSPROP, flags=R.CENTERED), ("s2",)), "no blocks": (dict(rule=R.ADAM), ("blocks",)),
+       "flag 16": (dict(rule=R.ADAM, flags=16), ()), "sgd + amsgrad": (dict(rule=R.SGD, flags=R.AMSGRAD), ()),
+       "sgd + centered": (dict(rule=R.SGD, flags=R.CENTERED), ()), "sgd + momentum flag": (dict(rule=R.SGD, flags=R.MOMENTUM), ()),
+       "rmsprop + nesterov": (dict(rule=R.RMSPROP, flags=R.NESTEROV), ()), "sgd without slot0": (dict(rule=R.SGD), ("s0",))}
 
 
 @pytest.mark.parametrize("case", list(BAD))
@@ -221,7 +224,7 @@ def test_engine_train_steps_follow_the_rule(cuda, engines, which):
 
 
 def test_engine_sgd_keeps_one_slot_arena(cuda, engines):
-    """back to SGD on the same engine: V alone, zero again, and the step is rn_optim_sgd_step's"""
+    """back to SGD on the same engine: V alone, zero again, and the step is the SGD rule's"""
     from retinanet.optimizers import build_optimizer
     p, model, eng, targets, images, _ = engines[0]
     _configure(engines[0], "adam+amsgrad")

@@ -245,6 +245,67 @@ def test_sgd_two_steps(cuda, layouts, which, build):
         assert not torch.equal(P, before[0])
 
 
+# ---- 5b. SGD bit for bit: both entry points against the float32 evaluation of the header's op order ----------------------------
+SGD_CASES = ((0, 0.9, True), (1, 0.9, False), (0, 0.0, False), (1, 0.0, True), (1, 0.9, True))   # (nesterov, momentum, ema)
+
+
+def _sgd_by(entry, a, P, G, V, E, Pbf, m, nesterov):
+    """one SGD launch through `entry`: rn_optim_sgd_step, or rn_optim_step with the RN_OPT_SGD rule (unused slots NULL)"""
+    import ctypes
+    from retinanet import _C
+    if entry == "rn_optim_sgd_step":
+        return a.sgd(P, G, V, E, Pbf, m, nesterov)
+    rule = _C.OptimRule(rule=_C.RN_OPT_SGD, flags=_C.RN_OPT_NESTEROV if nesterov else 0, lr=LR, momentum=m,
+                        ema_decay=DECAY if E is not None else 0.0)
+    _C.check(a.lib.rn_optim_step(_C.ptr(P), _C.ptr(G), _C.ptr(V), None, None, _C.ptr(E), _C.ptr(Pbf), _C.ptr(a.segs),
+                                 _C.ptr(a.bs), a.lay.n_blocks, ctypes.byref(rule), None, _C.current_stream()), "rn_optim_step")
+
+
+def _sgd_bits(entry, lay, cuda, build, nesterov, m, use_ema):
+    """Two steps through `entry` from _sgd_inputs; after each step every arena must equal O.emu_sgd's bit for bit, the
+    16-bit copy included, and every slot that is no tensor element must still hold its sentinel.  Returns the CPU arenas
+    (w, v, ema or None, 16-bit copy) after each step."""
+    m = O.f32(m)
+    a = Arena(lay, cuda, _lib(build))
+    P, G, V, E, Pbf = _sgd_inputs(lay, cuda, _DT[build])
+    g0 = G.cpu()
+    want = (P.cpu(), V.cpu(), E.cpu(), Pbf.cpu())
+    if not use_ema:
+        E = None
+    steps = []
+    for step in range(2):
+        _sgd_by(entry, a, P, G, V, E, Pbf, m, nesterov)
+        torch.cuda.synchronize()
+        want = O.emu_sgd(lay, want[0], g0, want[1], want[2], want[3], LR, m, DECAY, nesterov)
+        got = (P.cpu(), V.cpu(), None if E is None else E.cpu(), Pbf.cpu())
+        for name, x, y in zip(("w", "v", "ema", "16-bit copy"), got, want):
+            if x is not None:
+                assert torch.equal(x, y), (entry, build, nesterov, m, use_ema, step, name, int((x != y).sum()))
+                free = lay.untouched16 if name == "16-bit copy" else lay.untouched
+                assert bool((x[free] == (O.SENTINEL16 if name == "16-bit copy" else O.SENTINEL)).all()), (entry, step, name)
+        assert torch.equal(G.cpu(), g0)
+        steps.append(got)
+    return steps
+
+
+@pytest.mark.parametrize("build", ["bf16", "f16"])
+@pytest.mark.parametrize("which", ["a", "b"])
+def test_sgd_bit_for_bit_through_both_entry_points(cuda, layouts, which, build):
+    """rn_optim_sgd_step and rn_optim_step with the RN_OPT_SGD rule give the bits of the float32 NumPy evaluation of the
+    header's op order (optim_ref.emu_sgd), and each other's: w, v, ema and the 16-bit copy after each of two steps, on the
+    engine-like layout (16-byte body, short tails, a 9-block tensor, more than 256 tensors) and on offsets 1, 2, 3 mod 4
+    with the aligned-fp32 / unaligned-16-bit tensor.  Equality, no tolerance: this is what "the SGD step did not change"
+    means."""
+    lay = layouts[which]
+    for nesterov, m, use_ema in SGD_CASES:
+        one = _sgd_bits("rn_optim_sgd_step", lay, cuda, build, nesterov, m, use_ema)
+        two = _sgd_bits("rn_optim_step", lay, cuda, build, nesterov, m, use_ema)
+        for step, (s1, s2) in enumerate(zip(one, two)):
+            for name, x, y in zip(("w", "v", "ema", "16-bit copy"), s1, s2):
+                assert (x is None and y is None) or torch.equal(x, y), (nesterov, m, use_ema, step, name)
+        assert not torch.equal(one[1][0], one[0][0])
+
+
 # ---- 6. the skip flag in G[0] -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("build", ["bf16", "f16"])
 @pytest.mark.parametrize("which", ["a", "b"])

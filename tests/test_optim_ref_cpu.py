@@ -206,27 +206,6 @@ def emu_clip(lay, inp, fault=None):
     return torch.from_numpy(t_arena), torch.from_numpy(g), torch.from_numpy(cor), torch.tensor(metrics), torch.tensor(flags)
 
 
-def emu_sgd(lay, w, g, v, e, pbf, lr, m, d, nesterov, fault=None):
-    w, g, v, e = w.numpy().copy(), g.numpy(), v.numpy().copy(), e.numpy().copy()
-    pbf = pbf.clone()
-    lr, m, d = F32(lr), F32(m), F32(d)
-    for s in lay.segs:
-        o, n = int(s["offset"]), int(s["size"])
-        sl = slice(o, o + n)
-        vel = m * v[sl] - lr * g[sl]
-        old = v[sl] if fault == "nesterov_old_v" else vel
-        nw = w[sl] + ((m * old - lr * g[sl]) if nesterov else vel)
-        v[sl], w[sl] = vel, nw
-        k = d if fault == "ema_swapped" else F32(1.0) - d
-        e[sl] = e[sl] - k * (e[sl] - nw)
-        if s["bf"] >= 0:
-            x = torch.from_numpy(nw.copy())
-            if fault == "copy_truncates":
-                x = (x.view(torch.int32) & -65536).view(torch.float32)
-            pbf[int(s["bf"]):int(s["bf"]) + n] = x.to(pbf.dtype)
-    return torch.from_numpy(w), torch.from_numpy(v), torch.from_numpy(e), pbf
-
-
 @pytest.fixture(scope="module")
 def clip_runs(lay_a):
     """the right emulation of every regime, once"""
@@ -293,7 +272,7 @@ def test_rule_accepts_the_sgd_emulation(lay_a, lay_b, which, nesterov, m):
     w, g, v, e, pbf = _sgd_case(lay)
     lr, m, d = O.f32(0.1), O.f32(m), O.f32(0.9998)
     for step in range(2):
-        w1, v1, e1, p1 = emu_sgd(lay, w, g, v, e, pbf, lr, m, d, nesterov)
+        w1, v1, e1, p1 = O.emu_sgd(lay, w, g, v, e, pbf, lr, m, d, nesterov)
         r = O.verify_sgd(lay, (w, v, e), (w1, v1, e1), g, lr, m, d, nesterov, pbf, p1)
         assert O.worst(r) <= 1.0, (step, r)
         w, v, e, pbf = w1, v1, e1, p1
@@ -307,7 +286,7 @@ def test_rule_rejects_sgd_fault(lay_a, fault):
     nesterov, where = SGD_FAULTS[fault]
     w, g, v, e, pbf = _sgd_case(lay_a)
     lr, m, d = O.f32(0.1), O.f32(0.9), O.f32(0.9998)
-    w1, v1, e1, p1 = emu_sgd(lay_a, w, g, v, e, pbf, lr, m, d, nesterov, fault)
+    w1, v1, e1, p1 = O.emu_sgd(lay_a, w, g, v, e, pbf, lr, m, d, nesterov, fault)
     r = O.verify_sgd(lay_a, (w, v, e), (w1, v1, e1), g, lr, m, d, nesterov, pbf, p1)
     assert r[where] > 1.0, (fault, r)
 

@@ -212,6 +212,10 @@ def emu(lay, r, st, g, ema_on=True, fault=None):
                 nw = w - mom
             else:
                 nw = w - (lr * gg) / (np.sqrt(d) + eps)
+        elif r.rule == R.SGD:
+            vel = mom_c * s0 - lr * gg
+            arr["s0"][sl] = vel
+            nw = w + (mom_c * vel - lr * gg) if r.flags & R.NESTEROV else w + vel
         else:
             acc = s0 + gg * gg
             arr["s0"][sl] = acc

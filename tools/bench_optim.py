@@ -1,5 +1,5 @@
 """Micro-benchmark of the optimizer step kernels on the training engine's own arenas (ResNet50-640: the engine's real
-segment and block tables): rn_optim_sgd_step and every mode of rn_optim_step, alternated in one process — time per launch,
+segment and block tables): every mode of rn_optim_step, alternated in one process — time per launch,
 algorithmic bytes (arrays read + written) and bytes/s.
 python tools/bench_optim.py [--size 640] [--window 0.25] [--rounds 3] [--lib bf16|f16] [--no-ema]"""
 import argparse, ctypes, math, os, sys
@@ -8,8 +8,10 @@ sys.path.insert(0, os.path.join(ROOT, "retinanet-tensorflow2.x_amd"))
 import torch
 from retinanet import _C
 
-# mode -> (rule, flags, fp32 arrays read, fp32 arrays written) without the moving average (one more each with it)
-MODES = {"adam": (_C.RN_OPT_ADAM, 0, 4, 3), "adam+amsgrad": (_C.RN_OPT_ADAM, _C.RN_OPT_AMSGRAD, 5, 4),
+# mode -> (rule, flags, fp32 arrays read, fp32 arrays written) without the moving average (one more each with it);
+# `sgd` comes first: it is the base of the "vs sgd" column
+MODES = {"sgd": (_C.RN_OPT_SGD, 0, 3, 2), "sgd+nesterov": (_C.RN_OPT_SGD, _C.RN_OPT_NESTEROV, 3, 2),
+         "adam": (_C.RN_OPT_ADAM, 0, 4, 3), "adam+amsgrad": (_C.RN_OPT_ADAM, _C.RN_OPT_AMSGRAD, 5, 4),
          "rmsprop": (_C.RN_OPT_RMSPROP, 0, 3, 2), "rmsprop+momentum": (_C.RN_OPT_RMSPROP, _C.RN_OPT_MOMENTUM, 4, 3),
          "rmsprop+centered": (_C.RN_OPT_RMSPROP, _C.RN_OPT_CENTERED, 4, 3),
          "rmsprop+centered+momentum": (_C.RN_OPT_RMSPROP, _C.RN_OPT_CENTERED | _C.RN_OPT_MOMENTUM, 5, 4),
@@ -41,19 +43,13 @@ def main():
     args = (eng.Pbf.data_ptr(), eng.segs_dev.data_ptr(), eng.block_seg_dev.data_ptr(), eng.n_blocks)
     E = eng.E.data_ptr() if ema else None
 
-    def sgd():
-        return lib.rn_optim_sgd_step(eng.P.data_ptr(), eng.G.data_ptr(), eng.V.data_ptr(), E, *args, 1e-6, 0.9, 0.9998, 0,
-                                     None, st)
-
     def rule_call(rule, flags):
         r = _C.OptimRule(rule=rule, flags=flags, lr=1e-6, beta1=0.9, beta2=0.999, rho=0.9, momentum=0.9, epsilon=1e-7,
                          ema_decay=0.9998)
         return lambda: lib.rn_optim_step(eng.P.data_ptr(), eng.G.data_ptr(), eng.V.data_ptr(), S1.data_ptr(), S2.data_ptr(),
                                          E, *args, ctypes.byref(r), None, st)
 
-    calls = {"sgd": (sgd, 3, 2)}
-    for name, (rule, flags, rd, wr) in MODES.items():
-        calls[name] = (rule_call(rule, flags), rd, wr)
+    calls = {name: (rule_call(rule, flags), rd, wr) for name, (rule, flags, rd, wr) in MODES.items()}
 
     def timed(fn, name, reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
