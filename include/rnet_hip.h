@@ -506,6 +506,7 @@ int rn_act_bwd(const void* dz, const void* z, void* dy, int64_t n, int act, void
  *   (SyncBN: all-reduce `bsums` — after rn_bn_bwd_reduce, so dgamma / dbeta stay local like tf.gradients leaves them
  *    until the optimizer's cross-replica sum)
  *   rn_bn_bwd_apply    dy = scale*(g - sum_g/n - xhat*sum_gxhat/n); dres (+)= g
+ *   rn_bn_frozen_bwd   the backward of a FROZEN BatchNorm (below): dy = scale*g*m; dres (+)= g
  * All tensors bf16 [P,C] (P = N*H*W), per-channel arrays f32.
  */
 typedef struct {
@@ -587,6 +588,22 @@ int rn_bn_bwd_apply(const rn_bn_problem* problem, void* stream);
  * workgroup of the chunked elementwise form); 0 = this problem runs the grid-stride form (a segment's C/8 does not divide
  * 256), which does not support it — leave dy_colsum_partial NULL then. */
 int rn_bn_bwd_colsum_chunks(const rn_bn_problem* problem, int segment);
+/* Backward of a BatchNormalization that runs in INFERENCE mode inside the training step (layer.trainable = False under a
+ * trainable Conv2D: the `bn` / `*-bn` keys of training.freeze_variables).  The forward pass of such a layer is rn_bn_apply
+ * on a problem whose fwd[2C..4C) = (scale, shift) the caller filled once from the moving statistics (scale =
+ * gamma/sqrt(moving_var + eps), shift = beta - moving_mean*scale); this is its whole backward, one elementwise launch over
+ * all segments:
+ *   g = dz * act'(.);   dy = rb(scale * (g * sample_scale[n]));   dres (+)= g   (first write or fp32 add + one rounding,
+ *   per dres_accumulate; dres is not scaled by sample_scale)
+ * Gate sources, in this order: act = none — g = dz; relu / relu6 — the act_mask bits when every segment has them (with or
+ * without a residual input), else the stored z behind a residual add and u = y*scale + shift without one; swish — at the
+ * value rn_bn_apply fed to swish (rb(rb(u) + residual) with the residual tensor read again, the fp32 u without one).
+ * Segments may disagree on having a residual input (generic form; relu / relu6 then need z behind the residual add).
+ * y is read only by the gates that are a function of u.  Reads fwd[2C..4C) only; never touches sums, bsums, gamma, beta,
+ * moving_mean, moving_var, dgamma, dbeta or ext_chunks* — all may be NULL / 0.
+ * RN_EINVAL before any launch (dy is not written): C % 8 != 0, a missing dz, dy or fwd, a missing gate source, swish
+ * together with sample_scale, a set dy_colsum_partial (sum the stored dy with rn_bn_stats instead). */
+int rn_bn_frozen_bwd(const rn_bn_problem* problem, void* stream);
 
 /* backward of K6/K7/K8 */
 int rn_maxpool2d_nhwc_bwd(const void* x, const void* dy, void* dx, int N, int H, int W, int C, int k, int stride,

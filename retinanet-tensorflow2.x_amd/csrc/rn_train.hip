@@ -901,6 +901,111 @@ extern "C" int rn_bn_bwd_apply(const rn_bn_problem* p, void* stream) {
   return RN_OK;
 }
 
+// ---- backward of a FROZEN BatchNorm (inference mode inside the training step) under a trainable conv ----
+// z = act((y*scale + shift) [* m[n]] + residual) with a CONSTANT scale / shift table (fwd[2C..4C), filled by the caller
+// from the moving statistics): dy = rb(scale * (g * m[n])), g = dz * act'(.), dres (+)= g.  No mean / xhat term, no
+// reduction, no gamma / beta gradient.  Same threading as bn_apply_kernel / bn_bwd_apply_kernel; the gate is compiled in
+// (one uniform branch per stage, never a run-time test inside the unrolled 8-channel loops), and y is read only by
+// the gates that are a function of u = y*scale + shift: with the bit mask or without an activation the pass reads dz
+// (+ P*C/8 bytes) and nothing else.
+template <int G>
+__global__ void __launch_bounds__(TR_THREADS) bn_frozen_bwd_kernel(const BnArgs a) {
+  const BnSegDev& s = a.seg[blockIdx.y];
+  const int C8 = s.C >> 3;
+  const long long total = s.P * C8;
+  BN_ELEMENTWISE_RANGE();
+  const int c8 = (int)(first % C8);
+  float sc[8], shq[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    sc[q] = s.fwd[2 * s.C + c8 * 8 + q];
+    shq[q] = s.fwd[3 * s.C + c8 * 8 + q];
+  }
+  constexpr bool gate_u = G == G_U_RELU || G == G_U_RELU6 || G == G_SWISH || G == G_SWISH_RES;   // always reads y
+  constexpr bool gate_z = G == G_Z_RELU || G == G_Z_RELU6;                                       // always reads z
+  const bool from_u = !s.residual && (a.act == RN_ACT_RELU || a.act == RN_ACT_RELU6);
+  // the generic gate of a mixed problem, per segment: relu / relu6 from u without a residual input and from z behind
+  // one, swish always from u
+  const bool read_y = gate_u || (G == G_GENERIC && (from_u || a.act == RN_ACT_SWISH));
+  const bool read_z = gate_z || (G == G_GENERIC && !from_u && (a.act == RN_ACT_RELU || a.act == RN_ACT_RELU6));
+  const bool swish_res = G == G_SWISH_RES || (G == G_GENERIC && a.act == RN_ACT_SWISH && s.residual != nullptr);
+  for (long long i = first; i < last; i += step) {
+    bf8 g = unpack8(s.dz[i]);
+    if (G == G_MASK) {
+      const unsigned bits = s.mask[i];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) g.v[q] = ((bits >> q) & 1u) ? g.v[q] : 0.0f;
+    } else if (G != G_NONE) {
+      bf8 y = {}, z = {}, res = {};
+      if (read_y) y = unpack8(s.y[i]);
+      if (read_z) z = unpack8(s.z[i]);
+      if (swish_res) res = unpack8(s.residual[i]);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        float u = y.v[q] * sc[q] + shq[q];
+        if (swish_res) u = bn_swish_input(u, res.v[q]);
+        g.v[q] = grad_gate<G>(g.v[q], z.v[q], u, a.act, from_u);
+      }
+    }
+    bf8 o;
+    if (s.sample_scale) {   // drop_connect scales the BatchNorm branch only: dres below takes g as it is
+      const float m = s.sample_scale[(int)(i / C8) / (int)s.rows_per_sample];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) o.v[q] = sc[q] * (g.v[q] * m);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) o.v[q] = sc[q] * g.v[q];
+    }
+    s.dy[i] = pack8(o);
+    if (s.dres) {
+      if (s.dres_accumulate) {
+        const bf8 old = unpack8(s.dres[i]);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) g.v[q] += old.v[q];
+      }
+      s.dres[i] = pack8(g);
+    }
+  }
+}
+
+// the gate of the frozen pass: the stored bits wherever every segment of a relu / relu6 problem has them (the engine
+// allocates them for every such frozen layer, with or without a residual input), else what the live passes take
+static int bn_frozen_gate_mode(const rn_bn_problem* p) {
+  if (p->act == RN_ACT_RELU || p->act == RN_ACT_RELU6) {
+    int with_mask = 0;
+    for (int i = 0; i < p->num_segments; ++i) with_mask += p->seg[i].act_mask ? 1 : 0;
+    if (with_mask == p->num_segments) return G_MASK;
+  }
+  return bn_gate_mode(p);
+}
+
+extern "C" int rn_bn_frozen_bwd(const rn_bn_problem* p, void* stream) {
+  BnArgs a;
+  RN_CHECK_ARG(bn_fill(p, a, 0) == 0, "rn_bn_frozen_bwd: bad problem (C %% 8 == 0, 1..10 segments, no swish with sample_scale)");
+  RN_CHECK_ARG(a.act == RN_ACT_NONE || a.act == RN_ACT_RELU || a.act == RN_ACT_RELU6 || a.act == RN_ACT_SWISH,
+               "rn_bn_frozen_bwd: unknown activation");
+  const int mode = bn_frozen_gate_mode(p);
+  long long mx = 0;
+  for (int i = 0; i < a.nseg; ++i) {
+    const BnSegDev& s = a.seg[i];
+    RN_CHECK_ARG(s.dz && s.dy && s.fwd, "rn_bn_frozen_bwd: null tensor");
+    RN_CHECK_ARG(!s.colsum, "rn_bn_frozen_bwd: dy_colsum_partial is not supported (sum the stored dy with rn_bn_stats)");
+    const bool relu = a.act == RN_ACT_RELU || a.act == RN_ACT_RELU6;
+    const bool need_z = mode == G_Z_RELU || mode == G_Z_RELU6 || (mode == G_GENERIC && relu && s.residual);
+    const bool need_y = mode != G_NONE && mode != G_MASK && !need_z;
+    RN_CHECK_ARG(!need_z || s.z, "rn_bn_frozen_bwd: z needed for the activation mask");
+    RN_CHECK_ARG(!need_y || s.y, "rn_bn_frozen_bwd: y needed for the activation gate");
+    const long long t = s.P * (s.C / 8);
+    if (t > mx) mx = t;
+  }
+  const dim3 grid(bn_elementwise_grid(a, mx), a.nseg), block(TR_THREADS);
+#define BN_CALL_(G_) hipLaunchKernelGGL(bn_frozen_bwd_kernel<G_>, grid, block, 0, (hipStream_t)stream, a)
+  BN_DISPATCH_GATE(mode, BN_CALL_)
+#undef BN_CALL_
+  RN_CHECK_LAUNCH();
+  return RN_OK;
+}
+
 // ---- gradient of an activation without BN (prediction-free layers): dy = dz * mask(z) --------
 // none / relu / relu6 only: the host entry refuses swish, whose derivative is no function of z
 __global__ void __launch_bounds__(TR_THREADS)

@@ -54,6 +54,9 @@ class SmallMessages:
         self.count = 0             # messages sent since the step began
         self._c2_local = None      # this rank's sum(num-positives) + 1 until a message has taken it along
         self.c2_normalizer = None  # all_reduce_sum(...) / replicas, once that message is merged
+        # False: the step sends no SyncBN forward message (every BatchNorm frozen), so nothing can take the normaliser
+        # along — c2_normalizer stays None and RetinaNetLoss does its own all-reduce
+        self.has_carrier = True
 
     @property
     def through_c10d(self):
@@ -63,7 +66,7 @@ class SmallMessages:
     def begin_step(self, num_positives):
         self.count = 0
         self._c2_local = self.c2_normalizer = None
-        if self.sync_bn:    # sum(num-positives) + 1 of this rank (retinanet_loss.py:38): folded into SyncBN traffic
+        if self.sync_bn and self.has_carrier:    # sum(num-positives) + 1 of this rank (retinanet_loss.py:38): folded into SyncBN traffic
             # (a device kernel reads it: a host tensor, or one on another GPU, must be moved first)
             npos = num_positives.to(self.dev, torch.float32).contiguous()
             self._c2_local = torch.empty((1,), dtype=torch.float32, device=self.dev)

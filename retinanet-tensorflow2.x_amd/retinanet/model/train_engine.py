@@ -13,8 +13,11 @@ scheduled from the same static graph as the forward pass.
   * BatchNorm forward/backward are two-stage reductions; with `use_sync` and >1 rank the
     per-group [sum, sumsq] / [sum g, sum g*xhat] vectors are all-reduced between the stages
     (SyncBatchNormalization, model/utils.py:10-12);
-  * frozen layers (training.freeze_variables, executor.py:154-176) keep inference-mode BN folded
-    into their conv epilogue and get no backward at all;
+  * layers frozen whole (training.freeze_variables, executor.py:154-176) keep inference-mode BN folded
+    into their conv epilogue and get no backward at all; a frozen BatchNorm under a trainable conv
+    (the `bn` / `*-bn` keys) runs in inference mode inside the step: the raw conv launch, rn_bn_apply
+    with a constant scale / shift table, and one elementwise rn_bn_frozen_bwd in the backward pass —
+    no statistics, no reductions, no gamma / beta gradients, no SyncBN message (DESIGN.md section 7b);
   * parameters, gradients, momentum and EMA live in four flat fp32 arenas (conv kernels in the
     compute layout [Cout][R][S][Cin]); the optimizer is three multi-tensor launches and also
     refreshes the bf16 compute copy of every kernel.
@@ -34,7 +37,7 @@ import torch
 from retinanet import _C
 from .bottleneck import Bottleneck64, fused_blocks
 from .data_parallel import GradientOverlap, SmallMessages
-from .forward import (FoldedConvs, FusionState, conv_launch_name, conv_problem, dw_problem, half_activations, maxpool_step,
+from .forward import (FoldedConvs, FusionState, conv_launch_name, conv_problem, dw_problem, fold_bn, half_activations, maxpool_step,
                       output_view, padded_outputs, split_by_depth, stem_input, stem_pool_partner, stem_pool_step, stem_problem, tensor_readers,
                       topdown_step)
 
@@ -57,8 +60,10 @@ class BnGroup(NamedTuple):
     sums: torch.Tensor     # [sum | sumsq] of every segment + the slot C2 rides in (the SyncBN forward message)
     bsums: torch.Tensor    # [sum g | sum g*xhat] of every segment (the SyncBN backward message)
     ws: torch.Tensor       # workspace of the two-stage reductions (partial sums, ticket counters)
-    dys: list              # per op: gradient at the conv output, written by rn_bn_bwd_apply
+    dys: list              # per op: gradient at the conv output, written by rn_bn_bwd_apply / rn_bn_frozen_bwd
     ops: list
+    fwd: torch.Tensor = None   # [mean | invstd | scale | shift] of every segment
+    frozen: bool = False   # BatchNorm in inference mode under a trainable conv: fwd holds the folded moving statistics
 
 
 class BackwardStep:
@@ -285,6 +290,10 @@ class TrainEngine:
     def _bn_trainable(self, op):
         return op.get("bn") and (op["bn"] + "/gamma") not in self.frozen
 
+    def _bn_frozen(self, op):
+        """BatchNorm in inference mode under a trainable conv (the `bn` / `*-bn` freeze patterns)"""
+        return bool(op.get("bn")) and self._conv_trainable(op) and not self._bn_trainable(op)
+
     def _inference_form(self, op):
         return not self._conv_trainable(op) and not self._bn_trainable(op) and not self.requires.get(op["inp"])
 
@@ -329,11 +338,13 @@ class TrainEngine:
                                           "(the reference's `backbone` and `resnet_initial` freeze patterns match the "
                                           "auxillary head): backward through a frozen head is not built — freeze "
                                           "by patterns that leave `auxillary-head` trainable")
-        # a conv layer is "live" when its kernel trains; mixed frozen conv / live BN is not a shipped case
+        # a conv layer is "live" when its kernel trains.  Live conv + frozen BatchNorm is what the `bn` / `*-bn` freeze
+        # patterns produce (_bn_frozen); a frozen conv under a live BatchNorm comes out of none of the eight patterns
         for op in self.ops:
             if op["op"] in ("conv", "stem", "dwconv") and op.get("bn") and \
-                    self._conv_trainable(op) != bool(self._bn_trainable(op)):
-                raise NotImplementedError(f"{self._kvar(op)}: conv and its BatchNorm must be frozen together")
+                    not self._conv_trainable(op) and self._bn_trainable(op):
+                raise NotImplementedError(f"{self._kvar(op)}: a frozen conv under a trainable BatchNorm is not built "
+                                          "(no freeze pattern produces it)")
 
     # ---- flat parameter arenas ---------------------------------------------------------------------
     def _alloc_params(self):
@@ -448,6 +459,7 @@ class TrainEngine:
         for (off, n), bfo in self._bf_copies:
             self.Pbf[bfo:bfo + n].copy_(self.P[off:off + n])
         self.refresh_packs()
+        self._fill_frozen_bn()
 
     def _bind_optimizer(self, reset=False):
         """Slot arenas for the optimizer the model holds NOW (tests and tools replace `model.optimizer` after the engine
@@ -620,7 +632,7 @@ class TrainEngine:
         self.stem_k, self.stem_pad, self.Hp, self.Wp, self.stem_in = stem_input(self.tensors, self._stem_op(), B, self.h16,
                                                                                 dev)
         for op in self.ops:
-            if op["op"] in ("conv", "stem", "dwconv") and self._bn_trainable(op):
+            if op["op"] in ("conv", "stem", "dwconv") and (self._bn_trainable(op) or self._bn_frozen(op)):
                 self.raw[op["out"]] = torch.empty_like(self.t[op["out"]])
         # squeeze-excite: saved forward state per op + one shared workspace
         self.se_state = {}
@@ -675,6 +687,22 @@ class TrainEngine:
                     self.folded.stable(name, self.model.variables[name].to(self.dev, torch.float32).reshape(-1).clone())
         for fb in self.bneck.values():
             fb.load(self.model.variables, self.eps)
+        self._fill_frozen_bn()
+
+    def _fill_frozen_bn(self, groups=None):
+        """(scale, shift) of the frozen BatchNorm layers under trainable convs, from the model's moving statistics by the
+        inference engine's arithmetic (forward.fold_bn), into fwd[2C..4C) of their rn_bn_problem segments: constant until
+        weights are loaded again.  The mean / invstd rows stay zero: nothing reads them."""
+        for grp in (getattr(self, "bn_groups", {}).values() if groups is None else groups):
+            if not grp.frozen:
+                continue
+            off = 0
+            for op in grp.ops:
+                C = self.tensors[op["out"]][2]
+                scale, shift, _ = fold_bn(self.model.variables, op["bn"], None, self.eps, self.dev)
+                grp.fwd[4 * off + 2 * C:4 * off + 3 * C].copy_(scale)
+                grp.fwd[4 * off + 3 * C:4 * off + 4 * C].copy_(shift)
+                off += C
 
     # ---- helpers to build launches ---------------------------------------------------------------------
     def _conv_meta(self, p):
@@ -800,7 +828,10 @@ class TrainEngine:
     def _bn_pass(self, kind, pb, fn):
         """BatchNorm elementwise / reduction passes (HBM-bound): bench.py brackets them with events on the launch stream.
         Algorithmic bytes: apply = read y + write z (+ residual); bwd_reduce = read y + dz (+ z for the residual
-        layers' gate); bwd_apply = the same reads + write dy (+ dres, + its old value when accumulating)."""
+        layers' gate); bwd_apply = the same reads + write dy (+ dres, + its old value when accumulating); frozen_bwd =
+        read dz + the gate source rn_bn_frozen_bwd actually reads (the bits, else z behind a relu / relu6 residual add, y
+        for the other relu / relu6 / swish layers + the residual re-read of swish, nothing without an activation) + write
+        dy (+ dres as for bwd_apply)."""
         prof = self.hbm_profile
         if prof is None or (kind == "bn_bwd_reduce" and pb.seg[0].ext_chunks_bwd > 0):   # only the final pass is left
             return fn()
@@ -809,7 +840,16 @@ class TrainEngine:
             s = pb.seg[i]
             n = int(s.P) * int(s.C) * 2
             gate = (n // 16 if s.act_mask else n) if (s.residual and pb.act) else 0   # z, or its one-bit gate
-            if kind == "bn_apply":
+            if kind == "bn_frozen_bwd":
+                relu = pb.act in (_C.ACT_IDS["relu"], _C.ACT_IDS["relu6"])
+                if relu and all(pb.seg[j].act_mask for j in range(pb.num_segments)):
+                    gate = n // 16
+                elif relu:
+                    gate = n
+                else:
+                    gate = (n * (2 if s.residual else 1)) if pb.act else 0
+                byts += n + gate + n * (1 + ((2 if s.dres_accumulate else 1) if s.dres else 0))
+            elif kind == "bn_apply":
                 byts += n * (3 if s.residual else 2) + (n // 16 if s.act_mask else 0)
             elif kind == "bn_bwd_reduce":
                 byts += n * 2 + gate
@@ -831,15 +871,20 @@ class TrainEngine:
     def _bn_problem(self, ops, conv_problem=None):
         """BatchNorm problem over `ops` and its buffers (BnGroup).  With `conv_problem` (the launch that produces the raw outputs): the forward
         statistics' stage-1 partial sums are written by the conv epilogue (rn_conv_segment.bn_partial, one row per
-        128 output pixels) and rn_bn_stats only does the final ordered reduction."""
+        128 output pixels) and rn_bn_stats only does the final ordered reduction.
+        A frozen BatchNorm under a trainable conv (_bn_frozen) gets the same problem without anything the statistics, the
+        reductions or the gamma / beta gradients touch: y, z, residual, dz, dy, the gate bits and the constant fwd table."""
+        frozen = self._bn_frozen(ops[0])
         p = _C.BnProblem()
         p.num_segments = len(ops)
         p.act = _C.ACT_IDS[ops[0]["act"]]
         p.bessel = 0 if self.sync_bn else 1
         p.eps, p.momentum, p.count_scale = self.eps, self.momentum_bn, float(self.world if self.sync_bn else 1)
         csum = sum(self.tensors[o["out"]][2] for o in ops)
-        sums = torch.zeros((2 * csum + 1,), dtype=torch.float32, device=self.dev)   # + the slot C2 rides in
-        bsums = torch.zeros((2 * csum,), dtype=torch.float32, device=self.dev)
+        sums = bsums = None
+        if not frozen:
+            sums = torch.zeros((2 * csum + 1,), dtype=torch.float32, device=self.dev)   # + the slot C2 rides in
+            bsums = torch.zeros((2 * csum,), dtype=torch.float32, device=self.dev)
         fwd = torch.zeros((4 * csum,), dtype=torch.float32, device=self.dev)
         off = 0
         dys = []
@@ -854,19 +899,21 @@ class TrainEngine:
             s.residual = self.t[op["residual"]].data_ptr() if op.get("residual") else None
             s.dz = self.grad[op["out"]].data_ptr() if op["out"] in self.grad else None
             s.dres = None
-            s.sums = sums.data_ptr() + 4 * 2 * off
-            s.bsums = bsums.data_ptr() + 4 * 2 * off
             s.fwd = fwd.data_ptr() + 4 * 4 * off
-            s.gamma = self._pview(bn + "/gamma").data_ptr()
-            s.beta = self._pview(bn + "/beta").data_ptr()
-            s.moving_mean = self.bn_state[bn]["mm"].data_ptr()
-            s.moving_var = self.bn_state[bn]["mv"].data_ptr()
-            s.dgamma = self._pview(bn + "/gamma", self.G).data_ptr()
-            s.dbeta = self._pview(bn + "/beta", self.G).data_ptr()
+            if not frozen:
+                s.sums = sums.data_ptr() + 4 * 2 * off
+                s.bsums = bsums.data_ptr() + 4 * 2 * off
+                s.gamma = self._pview(bn + "/gamma").data_ptr()
+                s.beta = self._pview(bn + "/beta").data_ptr()
+                s.moving_mean = self.bn_state[bn]["mm"].data_ptr()
+                s.moving_var = self.bn_state[bn]["mv"].data_ptr()
+                s.dgamma = self._pview(bn + "/gamma", self.G).data_ptr()
+                s.dbeta = self._pview(bn + "/beta", self.G).data_ptr()
             s.P, s.C, s.dres_accumulate = y.shape[0] * y.shape[1] * y.shape[2], C, 0
-            if s.residual and op["act"] in ("relu", "relu6"):
+            if (s.residual or frozen) and op["act"] in ("relu", "relu6"):
                 # relu behind the residual add: the forward stores the gate as one bit per element, the two backward
-                # passes read P*C/8 bytes instead of z (rn_bn_segment.act_mask)
+                # passes read P*C/8 bytes instead of z (rn_bn_segment.act_mask).  Every relu / relu6 layer of a frozen
+                # BatchNorm: rn_bn_frozen_bwd then reads the bits instead of y or z
                 mk = torch.empty((int(s.P) * C // 8,), dtype=torch.uint8, device=self.dev)
                 self._keep.append(mk)
                 s.act_mask = mk.data_ptr()
@@ -881,6 +928,11 @@ class TrainEngine:
                 self.dc_masks[op["out"]] = (m, float(op["survival"]))
                 s.sample_scale, s.rows_per_sample = m.data_ptr(), y.shape[1] * y.shape[2]
             off += C
+        if frozen:
+            grp = BnGroup(p, None, None, None, dys, ops, fwd, True)
+            self._fill_frozen_bn([grp])
+            self._keep += [p, fwd] + dys
+            return grp
         fused = conv_problem is not None and self.fuse_bn_stats and conv_problem.out_dtype == _C.RN_DT_BF16
         if fused:
             for i in range(len(ops)):   # one row of partial sums per 128 output pixels of the kernel the dispatcher will run
@@ -892,7 +944,7 @@ class TrainEngine:
             for i in range(len(ops)):
                 conv_problem.seg[i].bn_partial = ws.data_ptr() + self.lib.rn_bn_partial_offset_bytes(ctypes.byref(p), i)
         self._keep += [p, sums, bsums, fwd, ws] + dys
-        return BnGroup(p, sums, bsums, ws, dys, ops)
+        return BnGroup(p, sums, bsums, ws, dys, ops, fwd)
 
     # ---- forward --------------------------------------------------------------------------------------
     def _launch_ops(self, op, done):
@@ -907,14 +959,16 @@ class TrainEngine:
         return self._group_ops(op["op"], grp)
 
     def _bn_train_step(self, launch, ops, conv_problem=None):
-        """Forward step of layers with a live BatchNorm: launch(st) writes the raw outputs -> batch statistics and
-        finalize -> rn_bn_apply (bracketed for bench.py's hbm_profile); registers the launch's BnGroup."""
+        """Forward step of live convs with a BatchNorm: launch(st) writes the raw outputs -> batch statistics and
+        finalize (live BatchNorm only) -> rn_bn_apply (bracketed for bench.py's hbm_profile); registers the launch's
+        BnGroup."""
         grp = self.bn_groups[ops[0]["out"]] = self._bn_problem(ops, conv_problem)
         lib, pb, prb = self.lib, grp.problem, ctypes.byref(grp.problem)
 
         def run(st):
             launch(st)
-            self._bn_stats_finalize(prb, grp.ws, grp.sums, st)
+            if not grp.frozen:   # (frozen: scale / shift are the constants _fill_frozen_bn wrote)
+                self._bn_stats_finalize(prb, grp.ws, grp.sums, st)
             self._bn_pass("bn_apply", pb, lambda: _C.check(lib.rn_bn_apply(prb, st), "rn_bn_apply"))
         return run
 
@@ -970,10 +1024,10 @@ class TrainEngine:
                 live_bn = bool(self._bn_trainable(ops[0]))
                 if any(bool(self._bn_trainable(o)) != live_bn for o in ops):
                     raise NotImplementedError("a conv group mixes frozen and live BatchNorm")
-                if live_bn:
+                if live_bn or self._bn_frozen(ops[0]):   # (frozen BatchNorm: no bn_partial epilogue in the conv)
                     pc = self._conv_problem(ops, lambda o: self.raw[o["out"]], raw_mode=True)
                     self.fwd_steps.append(self._bn_train_step(lambda st, pc=pc: self._launch_conv(pc, st, "conv(train)"),
-                                                              ops, conv_problem=pc))
+                                                              ops, conv_problem=pc if live_bn else None))
                 else:
                     for sub in split_by_depth(self.g, ops):
                         pc = self._conv_problem(sub, lambda o: self.t[o["out"]], raw_mode=False)
@@ -983,6 +1037,9 @@ class TrainEngine:
                 if not ops:
                     continue
                 live_bn = bool(self._bn_trainable(ops[0]))
+                if any(bool(self._bn_trainable(o)) != live_bn for o in ops):
+                    raise NotImplementedError("a conv group mixes frozen and live BatchNorm")
+                live_bn = live_bn or self._bn_frozen(ops[0])   # either way: raw output, then the BatchNorm step
                 pd = self._dw_problem(ops, (lambda o: self.raw[o["out"]]) if live_bn else (lambda o: self.t[o["out"]]))
                 self.dw_launches.append(("dw:" + (ops[0].get("group") or ops[0]["out"]), "fwd", pd, []))
                 prd = ctypes.byref(pd)
@@ -1030,6 +1087,8 @@ class TrainEngine:
                         for k, d in self.g.outputs.items()}
         self._bn_of_tensor = {o["out"]: (grp.problem, i, o, len(grp.ops))
                               for grp in self.bn_groups.values() for i, o in enumerate(grp.ops)}
+        # the loss normaliser (C2) rides in the step's first SyncBN forward message: only a live BatchNorm sends one
+        self.small.has_carrier = any(not grp.frozen for grp in self.bn_groups.values())
 
     def _src(self, name):
         return self.bal_src.get(name, self.t[name])
@@ -1123,7 +1182,8 @@ class TrainEngine:
                 dwp = torch.zeros((c["cout"], k, 8, 4), dtype=torch.float32, device=self.dev)
                 gview = self._pview(self._kvar(op), self.G).view(c["cout"], k, k, 3)
                 self._keep += [pw, wsw, dwp]
-                bn_bwd = self._bn_bwd_step(grp, grp.ws, profiled=False)   # (its two passes were never rows of hbm_profile)
+                # (the live form's two passes were never rows of hbm_profile)
+                bn_bwd = self._bn_frozen_bwd_step(grp) if grp.frozen else self._bn_bwd_step(grp, grp.ws, profiled=False)
 
                 def stem_bwd(st, bn_bwd=bn_bwd.run, pw=pw, wsw=wsw, dwp=dwp, gview=gview, k=k):
                     bn_bwd(st)
@@ -1344,6 +1404,15 @@ class TrainEngine:
             bracket("bn_bwd_apply", pb, lambda: _C.check(lib.rn_bn_bwd_apply(prb, st), "rn_bn_bwd_apply"))
         return BackwardStep(run, writes=[op["bn"] + sfx for op in grp.ops for sfx in ("/gamma", "/beta")])
 
+    def _bn_frozen_bwd_step(self, grp):
+        """Backward of the frozen BatchNorm layers of BnGroup `grp`: one elementwise pass dz -> dy (+ dres).  No
+        workspace, no SyncBN message, and no variable's gradient is completed by it."""
+        lib, pb, prb = self.lib, grp.problem, ctypes.byref(grp.problem)
+
+        def run(st):
+            self._bn_pass("bn_frozen_bwd", pb, lambda: _C.check(lib.rn_bn_frozen_bwd(prb, st), "rn_bn_frozen_bwd"))
+        return BackwardStep(run, writes=[])
+
     @staticmethod
     def _distinct_inputs(ops):
         """the ops whose input needs a gradient, split into launches whose segments read distinct inputs (they write
@@ -1365,8 +1434,9 @@ class TrainEngine:
         if not self._conv_trainable(ops[0]):
             raise NotImplementedError("backward through a frozen conv that sits above trainable layers")
         live_bn = bool(self._bn_trainable(ops[0]))
+        frozen_bn = self._bn_frozen(ops[0])
         # (a) gradient wrt the conv output
-        if live_bn:
+        if live_bn or frozen_bn:
             grp = self.bn_groups[ops[0]["out"]]
             pb = grp.problem
             for i, op in enumerate(ops):
@@ -1375,8 +1445,10 @@ class TrainEngine:
                 if op.get("residual") and self.requires.get(op["residual"]):
                     dres, first = self._grad_target(op["residual"], mark, balanced=False)
                     s.dres, s.dres_accumulate = dres.data_ptr(), 0 if first else 1
-            # (ws: stage 1 already written there by the dgrad launch that produced dz)
-            self.bwd_steps.append(self._bn_bwd_step(grp, self.bn_bwd_ws.get(id(pb), grp.ws)))
+            if frozen_bn:
+                self.bwd_steps.append(self._bn_frozen_bwd_step(grp))
+            else:   # (ws: stage 1 already written there by the dgrad launch that produced dz)
+                self.bwd_steps.append(self._bn_bwd_step(grp, self.bn_bwd_ws.get(id(pb), grp.ws)))
             dy_of = {op["out"]: grp.dys[i] for i, op in enumerate(ops)}
         else:
             dy_of = {}
@@ -1465,7 +1537,8 @@ class TrainEngine:
                 # what it stores on the way out (rn_bn_segment.dy_colsum_partial) — stage 1 of this reduction then never
                 # reads the dy tensor again (FPN + head-tower convs: 17 launches, ~1 ms of side-stream HBM reads per step;
                 # same-process A/B of the step with / without ANY bias-gradient launch: 29.73 / 29.50 ms).  Where
-                # rn_bn_bwd_colsum_chunks refuses a segment the separate pass stays.
+                # rn_bn_bwd_colsum_chunks refuses a segment, and in front of a frozen BatchNorm (rn_bn_frozen_bwd has no
+                # such epilogue), the separate pass stays.
                 fused_cs = False
                 if live_bn:
                     seg_of = [ops.index(op) for op in cops]
@@ -1497,11 +1570,11 @@ class TrainEngine:
         shared separable conv); data gradient = the forward kernel on (zero-upsampled) dy with the
         tap-reversed filter, accumulating into gradient buffers that already hold a contribution."""
         lib, B = self.lib, self.B
-        if self._bn_trainable(ops[0]):
+        if self._bn_trainable(ops[0]) or self._bn_frozen(ops[0]):
             grp = self.bn_groups[ops[0]["out"]]
             for i, op in enumerate(ops):
                 grp.problem.seg[i].dz = self.grad[op["out"]].data_ptr()
-            self.bwd_steps.append(self._bn_bwd_step(grp, grp.ws))
+            self.bwd_steps.append(self._bn_frozen_bwd_step(grp) if grp.frozen else self._bn_bwd_step(grp, grp.ws))
             dy_of = {op["out"]: grp.dys[i] for i, op in enumerate(ops)}
         else:
             dy_of = {op["out"]: self.grad[op["out"]] for op in ops}

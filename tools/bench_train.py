@@ -30,6 +30,10 @@ def main():
     ap.add_argument("--big-min-tiles", type=int, default=0, help="override the 256x256 kernel's minimum tile count")
     ap.add_argument("--wgrad-big-blocks", type=int, default=0)
     ap.add_argument("--wgrad-blocks", type=int, default=0, help="override the wgrad split-K target workgroup count")
+    ap.add_argument("--freeze", default=None, metavar="KEY[,KEY]",
+                    help="override training.freeze_variables (model/builder.py FREEZE_VARS_REGEX keys; '' = none)")
+    ap.add_argument("--hbm-profile", action="store_true",
+                    help="after the timed steps, one more step with the BatchNorm passes bracketed: per-pass totals")
     a = ap.parse_args()
     from retinanet.cfg import default_params
     from retinanet.dataloader import LabelEncoder
@@ -38,6 +42,9 @@ def main():
     dev = torch.device("cuda:0")
     opts = dict(conv_big_min_tiles=a.big_min_tiles or 0, wgrad_target_blocks=(a.wgrad_big_blocks or a.wgrad_blocks or 0))
     p = default_params(input_size=a.size)
+    if a.freeze is not None:
+        p.training.freeze_variables = [k for k in a.freeze.split(",") if k]
+    print("freeze_variables", list(p.training.freeze_variables))
     b = ModelBuilder(p, "train", device=dev)
     model = b()
     eng = TrainEngine(model, a.batch, frozen_regexes=[b.FREEZE_VARS_REGEX[n] for n in p.training.freeze_variables],
@@ -66,6 +73,19 @@ def main():
             t = [x.elapsed_time(y) for x, y in ((e0, e1), (e1, e2), (e2, e3), (e3, e4), (e4, e5))]
             print(f"encode {t[0]:.2f} fwd {t[1]:.2f} loss {t[2]:.2f} bwd {t[3]:.2f} opt {t[4]:.2f} total {sum(t):.2f} ms "
                   f"-> {a.batch / sum(t) * 1e3:.1f} img/s  loss {loss['weighted-loss'].item():.4f}")
+    if a.hbm_profile:
+        eng.hbm_profile = []
+        eng.forward(images)
+        model.loss(targets, preds, compute_grads=True, grad_scale=1.0)
+        eng.backward(model.loss.grads)
+        torch.cuda.synchronize()
+        rows, eng.hbm_profile = eng.hbm_profile, None
+        tot = {}
+        for e0, e1, kind, byts in rows:
+            n, ms, by = tot.get(kind, (0, 0.0, 0))
+            tot[kind] = (n + 1, ms + e0.elapsed_time(e1), by + byts)
+        print("hbm_profile " + "  ".join(f"{k}: {n} launches {ms:.3f} ms {by / 1e9:.2f} GB" for k, (n, ms, by) in
+                                         sorted(tot.items())))
 
 
 if __name__ == "__main__":
