@@ -96,7 +96,8 @@ int rn_anchor_match_encode_iou(const float* anchors, int64_t A, const float* gt_
  * (n_l = anchors on that level; pointers are host arrays of device pointers),
  * level_offsets host i64[num_levels+1] = anchor boundaries.  Targets are the flattened
  * outputs of rn_anchor_match_encode.  normalizer: device f32[1] (already all-reduced and
- * divided by replicas, retinanet_loss.py:46-49).  grad_scale multiplies both gradients
+ * divided by replicas, retinanet_loss.py:46-49 — or the moving average rn_loss_normalizer_ema
+ * keeps, enqueued before on the same stream).  grad_scale multiplies both gradients
  * (1/num_replicas, times the loss scale under fp16: executor.py:421-425).
  * out: losses f32[4] = {box-loss, class-loss, weighted-loss, normalizer}; d_class_logits[l],
  * d_box_preds[l] same shapes as the inputs (may be NULL arrays to skip the backward).
@@ -121,6 +122,15 @@ int rn_retinanet_loss_fwd_bwd_bf16(const float* const* class_logits, const float
                                    float label_smoothing, float delta, float box_loss_weight,
                                    float class_loss_weight, float grad_scale, float* losses, void* workspace,
                                    size_t workspace_bytes, void* stream);
+/* Moving-average loss normaliser (retinanet_loss.py:19-44, loss.normalizer.use_moving_average; Keras'
+ * moving_average_update, no zero-debias):
+ * state' = state - (state - (sum(num_positives[0..n)) + 1)) * (1 - momentum), three separately rounded f32 ops;
+ * writes state' to both *state and *normalizer (they may alias).  The sum of the integer-valued counts is exact in any
+ * order while it stays below 2^24.  One wave, stream-ordered, no host synchronisation.  RN_EINVAL before any launch
+ * for n <= 0 or a null pointer (*state is then left untouched). */
+int rn_loss_normalizer_ema(const float* num_positives /* device f32[n] */, int n, float momentum,
+                           float* state /* device f32[1], in/out */, float* normalizer /* device f32[1], out */,
+                           void* stream);
 /* IouPredictionLoss (loss_impl.py:108-131, retinanet_loss.py:72-82): sum-reduced MSE of the auxiliary head's raw f32
  * predictions iou_preds[l] f32[B*H_l*W_l][pred_pix_stride] (the anchors_per_location live channels in front: the
  * prediction conv writes a channel count padded to a multiple of 4; dense maps pass anchors_per_location) against iou_targets f32[B, A] (rn_anchor_match_encode_iou) where target > -1,

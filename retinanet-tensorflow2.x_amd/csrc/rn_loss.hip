@@ -476,6 +476,48 @@ extern "C" int rn_retinanet_loss_fwd_bwd_bf16(const float* const* class_logits, 
                      losses, workspace, workspace_bytes, stream);
 }
 
+// ---- moving-average loss normaliser (retinanet_loss.py:19-44, loss.normalizer.use_moving_average) --------------------
+// v = sum(num_positives[0..n)) + 1;  d = f32(1) - f32(momentum);  state' = state - ((state - v) * d): Keras'
+// moving_average_update under TF2, i.e. state.assign_sub((state - v) * (1 - momentum)) — three separately rounded f32
+// operations (contraction is off for that block: a product fused into the last subtraction gives other bits at about
+// one step in 400) and NO zero-debias: from the initial state 0 with momentum 0.99 the first normaliser is ~0.01 v.
+// v is a sum of integer-valued f32 counts: every partial sum is an integer, so the sum (and the + 1) is exact in any
+// order while it stays below 2^24 — the lane-strided adds and the butterfly below are bit-equal to a sequential sum
+// under that bound (16.7 M positive anchors per replica and step; a 1024^2 image has 196 k anchors).
+// One workgroup of one wave; lane 0 writes state' to *state and *normalizer (they may alias: both stores follow the
+// only load of *state in program order, in the one lane that did that load).
+__global__ void __launch_bounds__(64)
+loss_normalizer_ema_kernel(const float* __restrict__ num_positives, int n, float momentum, float* state,
+                           float* normalizer) {
+  float s = 0.0f;
+  for (int i = threadIdx.x; i < n; i += 64) s += num_positives[i];
+  s = rn_wave_sum(s);
+  if (threadIdx.x == 0) {
+    const float v = s + 1.0f;
+    const float d = 1.0f - momentum;
+    const float old = state[0];
+    const float diff = old - v;
+    float prod = diff * d;
+    // the rounded product in a register of its own: under -ffp-contract=fast the backend fuses it into the subtraction
+    // even past `#pragma clang fp contract(off)`; it cannot look through this (the Makefile builds with
+    // -ffp-contract=off, this keeps the bits under any flag)
+    asm volatile("" : "+v"(prod));
+    const float upd = old - prod;
+    state[0] = upd;
+    normalizer[0] = upd;
+  }
+}
+
+extern "C" int rn_loss_normalizer_ema(const float* num_positives, int n, float momentum, float* state,
+                                      float* normalizer, void* stream) {
+  RN_CHECK_ARG(num_positives && state && normalizer, "rn_loss_normalizer_ema: null argument");
+  RN_CHECK_ARG(n > 0, "rn_loss_normalizer_ema: bad n=%d", n);
+  hipLaunchKernelGGL(loss_normalizer_ema_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, num_positives, n, momentum,
+                     state, normalizer);
+  RN_CHECK_LAUNCH();
+  return RN_OK;
+}
+
 // ---- IoU-prediction loss of the auxiliary head (loss_impl.py:108-131, retinanet_loss.py:72-82) ------------------------
 // Per anchor with IoU target t (rn_anchor_match_encode_iou: -1 on every non-positive anchor) and raw f32 prediction x
 // (no sigmoid): sample_weight = t > -1, L = w (x - t)^2 summed over anchors, levels and images, divided by the same

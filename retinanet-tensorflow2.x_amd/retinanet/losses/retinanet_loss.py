@@ -7,9 +7,13 @@ every level's logits / box predictions (stored in `.grads` for the backward pass
 autograd tape of the reference is replaced by closed-form derivatives.
 
 Distributed: the normaliser is all-reduced over `process_group` exactly where the reference
-calls replica_context.all_reduce (retinanet_loss.py:46-49).
+calls replica_context.all_reduce (retinanet_loss.py:46-49).  With `loss.normalizer.use_moving_average` it is instead the
+reference's replica-local moving average of sum(num-positives) + 1 (retinanet_loss.py:19-44), a device scalar that
+rn_loss_normalizer_ema updates in front of the loss launches: no all-reduce, no zero-debias.
 """
 from __future__ import annotations
+
+import logging
 
 import torch
 
@@ -26,9 +30,14 @@ class RetinaNetLoss:
         self._box_loss_weight = float(params.box_loss_weight)
         self._class_loss_weight = float(params.class_loss_weight)
         self._auxillary_loss_weight = float(params.auxillary_loss_weight)
-        if params.normalizer.use_moving_average:
-            raise NotImplementedError("loss.normalizer.use_moving_average is false in every shipped config "
-                                      "and is out of scope (SURVEY §2.2 C6)")
+        # loss.normalizer.use_moving_average (retinanet_loss.py:19-35): a replica-local f32 scalar that starts at 0.0
+        # and is updated on the device by every call (rn_loss_normalizer_ema); created by the first call, on the
+        # device of its targets
+        self.use_moving_average_normalizer = bool(params.normalizer.use_moving_average)
+        self.moving_average_normalizer = None
+        if self.use_moving_average_normalizer:
+            self.normalizer_momentum = float(params.normalizer.momentum)
+            logging.warning("Using moving average loss normalizer with momentum: {}".format(self.normalizer_momentum))
         self._pg = process_group
         self._ws = None
         self.grads = None
@@ -60,7 +69,18 @@ class RetinaNetLoss:
         # normaliser = all_reduce_sum(sum(num-positives) + 1) / replicas  (retinanet_loss.py:38-49)
         from retinanet.distribute import global_normalizer
         R = self._num_replicas()
-        if normalizer is None:
+        if self.use_moving_average_normalizer:
+            # retinanet_loss.py:40-44: each replica updates and uses its own moving average — no all-reduce, no division
+            # by the replica count, whatever the caller handed in; the update runs on every call (forward pass)
+            if self.moving_average_normalizer is None:
+                self.moving_average_normalizer = torch.zeros((1,), dtype=torch.float32, device=dev)
+            npos = targets["num-positives"].to(dev, torch.float32).contiguous()
+            normalizer = self.moving_average_normalizer
+            with torch.cuda.device(dev):
+                _C.check(lib.rn_loss_normalizer_ema(_C.ptr(npos), npos.numel(), self.normalizer_momentum,
+                                                    _C.ptr(normalizer), _C.ptr(normalizer), _C.current_stream()),
+                         "rn_loss_normalizer_ema")
+        elif normalizer is None:
             normalizer = global_normalizer(targets["num-positives"].sum(), R, self._pg)
         else:
             normalizer = normalizer.reshape(1).to(torch.float32).contiguous()

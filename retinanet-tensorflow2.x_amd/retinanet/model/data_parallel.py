@@ -63,10 +63,12 @@ class SmallMessages:
         """the messages hop main stream -> c10d's stream -> main stream"""
         return self.sync_bn and self.native_comm is None
 
-    def begin_step(self, num_positives):
+    def begin_step(self, num_positives, carry_normalizer=True):
+        """carry_normalizer=False: the loss keeps a replica-local moving average (loss.normalizer.use_moving_average,
+        retinanet_loss.py:40-44) and all-reduces nothing — the C2 slot stays empty, as without a carrier."""
         self.count = 0
         self._c2_local = self.c2_normalizer = None
-        if self.sync_bn and self.has_carrier:    # sum(num-positives) + 1 of this rank (retinanet_loss.py:38): folded into SyncBN traffic
+        if self.sync_bn and self.has_carrier and carry_normalizer:    # sum(num-positives) + 1 of this rank (retinanet_loss.py:38): folded into SyncBN traffic
             # (a device kernel reads it: a host tensor, or one on another GPU, must be moved first)
             npos = num_positives.to(self.dev, torch.float32).contiguous()
             self._c2_local = torch.empty((1,), dtype=torch.float32, device=self.dev)

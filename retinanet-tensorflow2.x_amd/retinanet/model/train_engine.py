@@ -567,6 +567,13 @@ class TrainEngine:
         if self.loss_scale:   # Keras' LossScaleOptimizer checkpoints its dynamic state the same way
             extra["loss_scale/current_loss_scale"] = np.asarray(self.loss_scale["scale"], dtype=np.float32)
             extra["loss_scale/good_steps"] = np.asarray(self.loss_scale["good"], dtype=np.int64)
+        loss = self.model.loss
+        if loss is not None and loss.use_moving_average_normalizer:
+            # this rank's value (only the chief writes checkpoints; the reference reads the ON_READ variable as the
+            # mean over the replicas: DESIGN 7c)
+            state = loss.moving_average_normalizer   # None before the first loss call: the initial 0.0
+            extra["loss/moving_average_normalizer"] = (np.zeros((), np.float32) if state is None
+                                                       else state.cpu().numpy().reshape(()).copy())
         self.model.save_weights(prefix, slots=self.optimizer_slots(), extra=extra)
 
     def restore_checkpoint(self, prefix):
@@ -599,6 +606,12 @@ class TrainEngine:
                 good = self.model.loaded_extras.get("loss_scale/good_steps")
                 self.loss_scale = dict(scale=float(ls), good=int(good) if good is not None else 0,
                                        growth_steps=int(opt.loss_scale_growth_steps), skipped=False)
+            man = self.model.loaded_extras.get("loss/moving_average_normalizer")
+            loss = self.model.loss
+            if man is not None and loss is not None and loss.use_moving_average_normalizer:
+                # a file without the key leaves the state as it is (0.0 in a fresh engine, the reference's initial value)
+                loss.moving_average_normalizer = torch.from_numpy(
+                    np.asarray(man, dtype=np.float32).reshape(1).copy()).to(self.dev)
 
     def store_to_model(self, use_ema=False):
         """flat arenas -> model.variables (executor.assign_moving_averaged_weights when use_ema)."""
@@ -2046,7 +2059,10 @@ class TrainEngine:
             self._bind_optimizer()          # slot arenas of the rule `opt` names (a no-op unless the optimizer was replaced)
             alpha = cfg.weight_decay_alpha if cfg.use_weight_decay else 0.0
             self._prepack_dgrad_weights()
-            self.small.begin_step(targets["num-positives"])
+            # the moving-average normaliser is replica-local: nothing of it rides in the SyncBN messages, and
+            # c2_normalizer stays None for the loss call below
+            self.small.begin_step(targets["num-positives"],
+                                  carry_normalizer=not self.model.loss.use_moving_average_normalizer)
             preds = self.forward(images)
             self._resolve_loss_scale()      # the previous step's "gradients not finite" flag: long since on the host
             step = self.step_count
