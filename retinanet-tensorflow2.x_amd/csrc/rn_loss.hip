@@ -17,6 +17,8 @@
 
 #define RN_LOSS_THREADS 256
 #define RN_LOSS_MAX_LEVELS 8
+// focal gradient: above this logit a positive's p - ys is taken from 1 - p instead of p - 1 (focal_elem)
+#define RN_FOCAL_SWITCH_X 4.0f
 
 struct LossLevels {
   int num_levels;
@@ -75,10 +77,17 @@ __device__ __forceinline__ void focal_elem(float x, bool pos, float alpha, float
   const float mod = gamma == 1.5f ? q * __builtin_amdgcn_sqrtf(q) : (q > 0.0f ? hw_exp2(gamma * hw_log2(q)) : 0.0f);
   loss = a_t * mod * ce;
   const float dmod = pos ? -gamma * p * mod : gamma * omp * mod;
-  grad = a_t * (mod * (p - ys) + ce * dmod);
+  // p - ys of a positive with x > 4 as -(1 - p) - (ys - 1), from omp: there p rounds towards 1 and p - 1 loses
+  // -(1 - p), in the end the whole first term of the gradient (40 % of it at gamma = 1.5 from x ~ 17 on).  ys - 1 is
+  // exact (ys in [0.5, 1]).  Everywhere else p - ys keeps the bits it always had: a negative (p - ls / 2) has nothing to
+  // lose, and up to x = 4 (1 - p >= 0.018) p - 1 is off by at most 2^-24 / 0.018 = 3e-6 of the term, no more than the
+  // rest of the formula (tests/loss_ref.py: the worst error of the restatement is 3.9e-6 with the switch at 0 or 3,
+  // 4.2e-6 at 4, 1.2e-5 at 5).  A step that holds no such positive computes exactly what it did before.
+  const float pmy = (pos && x > RN_FOCAL_SWITCH_X) ? -omp - (ys - 1.0f) : p - ys;
+  grad = a_t * (mod * pmy + ce * dmod);
 }
 
-// ---- K % 4 == 0 (every shipped config: 80 / 90 / 20 classes): four logits per thread and iteration ------------------
+// ---- K % 4 == 0 (the 80- and 20-class configs; 90 classes take focal_kernel<1> below): four logits per thread and iteration
 // The first version (focal_kernel<4> below, kept for V = 1) found its level with a loop over lv.vbeg and fetched the
 // level's pointers / sizes with dynamically indexed loads from the kernel-argument segment IN FRONT of every logit load
 // (two dependent memory round trips per iteration), divided three times per iteration, and spent ~62 VALU issue cycles
@@ -133,7 +142,10 @@ __device__ __forceinline__ void focal_pair(loss_f2 x, bool pos0, bool pos1, floa
   loss = a_t * mod * ce;
   const loss_f2 dm = {pos0 ? -p.x : omp.x, pos1 ? -p.y : omp.y};
   const loss_f2 dmod = f2_splat(gamma) * dm * mod;
-  grad = a_t * (mod * (p - ys) + ce * dmod);
+  // p - ys; for a positive with x > 4 without the cancellation of p - 1 (see focal_elem): -(1 - p) - (ys - 1)
+  const loss_f2 old = p - ys, fix = -ti - (ys - f2_splat(1.0f));
+  const loss_f2 pmy = {(pos0 && x.x > RN_FOCAL_SWITCH_X) ? fix.x : old.x, (pos1 && x.y > RN_FOCAL_SWITCH_X) ? fix.y : old.y};
+  grad = a_t * (mod * pmy + ce * dmod);
 }
 
 template <bool G15>
