@@ -28,6 +28,7 @@ max-pool has a gather-form backward.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 from typing import NamedTuple
 
@@ -78,6 +79,37 @@ class BackwardStep:
 
     def __call__(self, st):
         return self.run(st)
+
+
+class GradientJoins:
+    """Who writes an activation-gradient buffer first and who accumulates, decided once while the backward pass is planned:
+    the steps run in the order they are planned, so the first step that asks for a buffer stores into it and every later
+    one adds.  `buffers`: key -> gradient buffer (any mapping: the class only looks keys up); `balanced`: the pyramid levels
+    whose readers read BalanceFeatures' copy, so their gradient goes to the `bal:` key.  writers: key -> the labels of the
+    steps that wrote it, in order."""
+
+    def __init__(self, buffers, balanced=()):
+        self.buffers, self.balanced = buffers, balanced
+        self.writers = {}
+
+    def add(self, name, label, balanced=True):
+        """(gradient buffer of tensor `name`, accumulate: an earlier step has written it) for a step that can do either.
+        balanced=False: the step's forward read the tensor itself, not the balanced copy (residual inputs)."""
+        key = "bal:" + name if balanced and name in self.balanced else name
+        buf = self.buffers[key]
+        before = self.writers.setdefault(key, [])
+        before.append(label)
+        return buf, len(before) > 1
+
+    def sole(self, name, label):
+        """Gradient buffer of tensor `name` for a step whose kernel overwrites it: an earlier writer's contribution would
+        be lost, so there must be none."""
+        buf = self.buffers[name]
+        before = self.writers.setdefault(name, [])
+        if before:
+            raise RuntimeError(f"{label} overwrites the gradient of {name}, which {before[0]} has already written")
+        before.append(label)
+        return buf
 
 
 class TrainEngine:
@@ -971,6 +1003,14 @@ class TrainEngine:
         done.add((op["op"], grp))
         return self._group_ops(op["op"], grp)
 
+    def _launch_ops_bn(self, op, done):
+        """(_launch_ops(op, done), whether the launch's BatchNorm trains): one launch has one BatchNorm form"""
+        ops = self._launch_ops(op, done)
+        live_bn = bool(ops) and bool(self._bn_trainable(ops[0]))
+        if any(bool(self._bn_trainable(o)) != live_bn for o in ops):
+            raise NotImplementedError("a conv group mixes frozen and live BatchNorm")
+        return ops, live_bn
+
     def _bn_train_step(self, launch, ops, conv_problem=None):
         """Forward step of live convs with a BatchNorm: launch(st) writes the raw outputs -> batch statistics and
         finalize (live BatchNorm only) -> rn_bn_apply (bracketed for bench.py's hbm_profile); registers the launch's
@@ -1031,12 +1071,9 @@ class TrainEngine:
                                     (lprof, ("fwd:" + fb.name, fb.flops, fb.bytes, "bneck64_kernel (one launch per block)")))
                     self.fwd_steps.append(run_block)
             elif kind == "conv":
-                ops = self._launch_ops(op, done)
+                ops, live_bn = self._launch_ops_bn(op, done)
                 if not ops:
                     continue
-                live_bn = bool(self._bn_trainable(ops[0]))
-                if any(bool(self._bn_trainable(o)) != live_bn for o in ops):
-                    raise NotImplementedError("a conv group mixes frozen and live BatchNorm")
                 if live_bn or self._bn_frozen(ops[0]):   # (frozen BatchNorm: no bn_partial epilogue in the conv)
                     pc = self._conv_problem(ops, lambda o: self.raw[o["out"]], raw_mode=True)
                     self.fwd_steps.append(self._bn_train_step(lambda st, pc=pc: self._launch_conv(pc, st, "conv(train)"),
@@ -1046,12 +1083,9 @@ class TrainEngine:
                         pc = self._conv_problem(sub, lambda o: self.t[o["out"]], raw_mode=False)
                         self.fwd_steps.append(lambda st, pc=pc: self._launch_conv(pc, st, "conv"))
             elif kind == "dwconv":
-                ops = self._launch_ops(op, done)
+                ops, live_bn = self._launch_ops_bn(op, done)
                 if not ops:
                     continue
-                live_bn = bool(self._bn_trainable(ops[0]))
-                if any(bool(self._bn_trainable(o)) != live_bn for o in ops):
-                    raise NotImplementedError("a conv group mixes frozen and live BatchNorm")
                 live_bn = live_bn or self._bn_frozen(ops[0])   # either way: raw output, then the BatchNorm step
                 pd = self._dw_problem(ops, (lambda o: self.raw[o["out"]]) if live_bn else (lambda o: self.t[o["out"]]))
                 self.dw_launches.append(("dw:" + (ops[0].get("group") or ops[0]["out"]), "fwd", pd, []))
@@ -1106,143 +1140,47 @@ class TrainEngine:
     def _src(self, name):
         return self.bal_src.get(name, self.t[name])
 
-    def _grad_target(self, name, mark, balanced=True):
-        """(gradient buffer of tensor `name`, True when the caller is its first writer in the backward order — `mark` is
-        _build_backward's record of that).  A reader of a balanced pyramid level read BalanceFeatures' copy, so its gradient
-        goes to the `bal:` buffer; balanced=False: the reader took the tensor itself (residual inputs)."""
-        key = "bal:" + name if balanced and name in self.bal_src else name
-        return self.grad[key], mark(key)
-
-    def _zero_upsampled(self, dy, H, W):
-        """dy of a stride-2 layer with zeros between its pixels, at the layer input's H x W: (buffer, the rn_upsample_zero2x
-        arguments that fill it).  The stride-1 form of the data gradient then runs on it."""
+    def _zero_upsampled(self, dy, H, W, ups):
+        """dy of a stride-2 layer with zeros between its pixels, at the layer input's H x W, for the stride-1 form of the
+        data gradient to run on.  The rn_upsample_zero2x arguments that fill the buffer join `ups`, which _dgrad_step runs."""
         up = torch.empty((self.B, H, W, dy.shape[3]), dtype=self.h16, device=self.dev)
         self._keep.append(up)
-        return up, (dy.data_ptr(), up.data_ptr(), self.B, dy.shape[1], dy.shape[2], dy.shape[3], H, W)
+        ups.append((dy.data_ptr(), up.data_ptr(), self.B, dy.shape[1], dy.shape[2], dy.shape[3], H, W))
+        return up
+
+    def _dgrad_step(self, ups, launch, post_op=None, post=(), what="dgrad"):
+        """Data-gradient step: rn_upsample_zero2x over the argument tuples `ups` (_zero_upsampled), launch(st), then
+        post_op = (library function, its name) over the argument tuples `post`.  launch(st) returns the library's status, or
+        None where it has checked it itself (_launch_conv)."""
+        lib = self.lib
+
+        def dgrad(st):
+            for u in ups:
+                _C.check(lib.rn_upsample_zero2x(*u, st), "rn_upsample_zero2x")
+            status = launch(st)
+            if status:
+                _C.check(status, what)
+            for a in post:
+                _C.check(post_op[0](*a, st), post_op[1])
+        return BackwardStep(dgrad)
 
     # ---- backward ---------------------------------------------------------------------------------------
     def _build_backward(self):
-        lib, B = self.lib, self.B
         self.bwd_steps = []
         self.dgrad_packs = []     # (master offset, conv dims, packed buffer)
-        ops = self.ops
         self.dw_flip_packs = []   # (master offset, k, C, packed bf16 tap-reversed filter)
         plan, done = [], set()
-        for op in ops:     # the forward launches; a group stands where its first op does
+        for op in self.ops:     # the forward launches; a group stands where its first op does
             if op["op"] in ("conv", "dwconv"):
                 launch = self._launch_ops(op, done)
                 if launch:
                     plan.append((op["op"], launch))
-            elif op["op"] in ("maxpool", "topdown", "balance", "stem", "se"):
+            elif op["op"] in self._backward_planners:
                 plan.append((op["op"], op))
-        plan.reverse()
-        # which tensor gradients get more than one contribution is decided at build time
-        written = set()
-
-        def mark(name):
-            first = name not in written
-            written.add(name)
-            return first
-
-        for kind, item in plan:
-            if kind == "conv":
-                self._plan_conv_backward(item, mark)
-            elif kind == "dwconv":
-                self._plan_dw_backward(item, mark)
-            elif kind == "se":
-                op = item
-                x, dy, dx = self.t[op["inp"]], self.grad[op["out"]], self.grad[op["inp"]]
-                mark(op["inp"])
-                name, se = op["se"], self.g.ses[op["se"]]
-                a = (x.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, x.shape[1] * x.shape[2], se["C"],
-                     self.Pbf.data_ptr() + 2 * self.bf_off[name + ":w1"],
-                     self.Pbf.data_ptr() + 2 * self.bf_off[name + ":w2"], se["se"], self.se_state[op["out"]].data_ptr(),
-                     self._pview(name + "/conv2d/kernel", self.G).data_ptr(),
-                     self._pview(name + "/conv2d/bias", self.G).data_ptr(),
-                     self._pview(name + "/conv2d_1/kernel", self.G).data_ptr(),
-                     self._pview(name + "/conv2d_1/bias", self.G).data_ptr(), self.se_ws.data_ptr(), self.se_ws.numel())
-                self.se_launches.append(("se:" + op["out"], "bwd", B, x.shape[1] * x.shape[2], se["C"], se["se"]))
-                self.bwd_steps.append(BackwardStep(
-                    lambda st, a=a: _C.check(lib.rn_squeeze_excite_bwd(*a, st), "rn_squeeze_excite_bwd"),
-                    writes=[name + sfx for sfx in ("/conv2d/kernel", "/conv2d/bias", "/conv2d_1/kernel", "/conv2d_1/bias")]))
-            elif kind == "maxpool":
-                op = item
-                if not self.requires.get(op["inp"]):
-                    continue
-                x, dy, dx = self.t[op["inp"]], self.grad[op["out"]], self.grad[op["inp"]]
-                acc = 0 if mark(op["inp"]) else 1
-                a = (x.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, x.shape[1], x.shape[2], x.shape[3], op["k"],
-                     op["stride"], op["pad_top"], op["pad_left"], dy.shape[1], dy.shape[2], acc)
-                self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_maxpool2d_nhwc_bwd(*a, st), "maxpool_bwd")))
-            elif kind == "stem":
-                op = item
-                if not self._conv_trainable(op):
-                    continue
-                grp = self.bn_groups[op["out"]]
-                grp.problem.seg[0].dz = self.grad[op["out"]].data_ptr()
-                dy = grp.dys[0]
-                c = self.g.convs[op["conv"]]
-                pw = _C.WgradProblem()
-                pw.opts = self.launch_opts
-                k = self.stem_k
-                pw.R, pw.S, pw.stride_h, pw.stride_w, pw.pad_top, pw.pad_left, pw.num_segments = k, 1, 2, 2, 0, 0, 1
-                sg = pw.seg[0]
-                sg.x, sg.dy = self.stem_in.data_ptr(), dy.data_ptr()
-                sg.N, sg.H, sg.W, sg.Cin, sg.Ho, sg.Wo, sg.Cout = B, self.Hp, self.Wp, 32, dy.shape[1], dy.shape[2], c["cout"]
-                sg.x_pix_stride = 4
-                wsw = torch.empty((max(lib.rn_wgrad_workspace_bytes(ctypes.byref(pw)), 256),), dtype=torch.uint8,
-                                  device=self.dev)
-                dwp = torch.zeros((c["cout"], k, 8, 4), dtype=torch.float32, device=self.dev)
-                gview = self._pview(self._kvar(op), self.G).view(c["cout"], k, k, 3)
-                self._keep += [pw, wsw, dwp]
-                # (the live form's two passes were never rows of hbm_profile)
-                bn_bwd = self._bn_frozen_bwd_step(grp) if grp.frozen else self._bn_bwd_step(grp, grp.ws, profiled=False)
-
-                def stem_bwd(st, bn_bwd=bn_bwd.run, pw=pw, wsw=wsw, dwp=dwp, gview=gview, k=k):
-                    bn_bwd(st)
-                    _C.check(lib.rn_conv2d_nhwc_wgrad(ctypes.byref(pw), dwp.data_ptr(), 0.0, wsw.data_ptr(),
-                                                      wsw.numel(), st), "stem wgrad")
-                    gview.copy_(dwp[:, :, :k, :3])   # [co][r][8 taps x 4 ch] -> [co][r][s][c]
-                self.bwd_steps.append(BackwardStep(stem_bwd, writes=[self._kvar(op)] + bn_bwd.writes))
-            elif kind == "topdown":
-                op = item
-                L = len(op["ins"])
-                if op["act"] == "swish":
-                    # rn_fpn_topdown_bwd_level refuses it: swish' needs the sum in front of the activation, and the
-                    # forward pass keeps only its output
-                    raise NotImplementedError(f"backward of the top-down op {op['outs'][0]} .. {op['outs'][-1]} with "
-                                              "activation 'swish' is not built (relu / relu6 / none are)")
-                act = _C.ACT_IDS[op["act"]]
-                if op.get("fusion"):
-                    self._plan_fused_topdown_backward(op, act, mark)
-                    continue
-                prev = None
-                for l in range(L):
-                    dout = self.grad[op["outs"][l]]
-                    din = self.grad[op["ins"][l]]
-                    mark(op["ins"][l])
-                    outp = self.t[op["outs"][l]].data_ptr() if l < L - 1 else None
-                    a = (dout.data_ptr(), prev, outp, din.data_ptr(), B, dout.shape[1], dout.shape[2], dout.shape[3],
-                         act if l < L - 1 else _C.RN_ACT_NONE)
-                    self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_fpn_topdown_bwd_level(*a, st),
-                                                                                "topdown_bwd")))
-                    prev = din.data_ptr()
-            elif kind == "balance":
-                op = item
-                names = op["tensors"]
-                dout = [self.grad["bal:" + n] for n in names]
-                ins = [self.t[n] for n in names]
-                din = [self.grad[n] for n in names]
-                for n in names:
-                    mark(n)
-                nsc = lib.rn_balance_features_bwd_scratch_bytes(len(names), op["mid"], B, ins[0].shape[1], ins[0].shape[2],
-                                                                ins[0].shape[3])
-                scratch = torch.empty((max(int(nsc), 256),), dtype=torch.uint8, device=self.dev)
-                pd, pi, pn = _C.ptr_array(dout), _C.ptr_array(ins), _C.ptr_array(din)
-                self._keep += [pd, pi, pn, scratch]
-                a = (pd, pi, pn, self.bal_avg.data_ptr(), scratch.data_ptr(), scratch.numel(), len(names), op["mid"], B,
-                     ins[0].shape[1], ins[0].shape[2], ins[0].shape[3])
-                self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_balance_features_bwd(*a, st), "balance_bwd")))
+        # which tensor gradients get more than one contribution is decided here, by the order the steps are planned in
+        self.joins = joins = GradientJoins(self.grad, self.bal_src)
+        for kind, item in reversed(plan):
+            self._backward_planners[kind](self, item, joins)
         # what the steps look up, static from here on
         self._launch_names = {id(q): n for n, q in self.conv_launches}
         # (a frozen prediction conv has no dy: such an engine serves forward() only)
@@ -1255,7 +1193,115 @@ class TrainEngine:
                 arr[i].R, arr[i].S, arr[i].Cin, arr[i].Cout, arr[i].Cout_pad, arr[i].pad_ = k, k, cin, cout, cw, mode
             self._dgrad_pack_items = arr
 
-    def _plan_fused_topdown_backward(self, op, act, mark):
+    def _plan_se_backward(self, op, joins):
+        lib, B = self.lib, self.B
+        x, dy = self.t[op["inp"]], self.grad[op["out"]]
+        dx = joins.sole(op["inp"], "se:" + op["out"])
+        name, se = op["se"], self.g.ses[op["se"]]
+        a = (x.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, x.shape[1] * x.shape[2], se["C"],
+             self.Pbf.data_ptr() + 2 * self.bf_off[name + ":w1"],
+             self.Pbf.data_ptr() + 2 * self.bf_off[name + ":w2"], se["se"], self.se_state[op["out"]].data_ptr(),
+             self._pview(name + "/conv2d/kernel", self.G).data_ptr(),
+             self._pview(name + "/conv2d/bias", self.G).data_ptr(),
+             self._pview(name + "/conv2d_1/kernel", self.G).data_ptr(),
+             self._pview(name + "/conv2d_1/bias", self.G).data_ptr(), self.se_ws.data_ptr(), self.se_ws.numel())
+        self.se_launches.append(("se:" + op["out"], "bwd", B, x.shape[1] * x.shape[2], se["C"], se["se"]))
+        self.bwd_steps.append(BackwardStep(
+            lambda st, a=a: _C.check(lib.rn_squeeze_excite_bwd(*a, st), "rn_squeeze_excite_bwd"),
+            writes=[name + sfx for sfx in ("/conv2d/kernel", "/conv2d/bias", "/conv2d_1/kernel", "/conv2d_1/bias")]))
+
+    def _plan_maxpool_backward(self, op, joins):
+        lib, B = self.lib, self.B
+        if not self.requires.get(op["inp"]):
+            return
+        x, dy = self.t[op["inp"]], self.grad[op["out"]]
+        dx, accumulate = joins.add(op["inp"], "maxpool:" + op["out"], balanced=False)
+        a = (x.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, x.shape[1], x.shape[2], x.shape[3], op["k"],
+             op["stride"], op["pad_top"], op["pad_left"], dy.shape[1], dy.shape[2], int(accumulate))
+        self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_maxpool2d_nhwc_bwd(*a, st), "maxpool_bwd")))
+
+    def _plan_stem_backward(self, op, joins):
+        lib, B = self.lib, self.B
+        if not self._conv_trainable(op):
+            return
+        # the BatchNorm step runs inside stem_bwd, ahead of the weight gradient (the live form's two passes were never rows
+        # of hbm_profile)
+        head = []
+        dy = self._plan_bn_backward([op], joins, profiled=False, steps=head)[op["out"]]
+        bn_bwd = head[0]
+        c = self.g.convs[op["conv"]]
+        pw = _C.WgradProblem()
+        pw.opts = self.launch_opts
+        k = self.stem_k
+        pw.R, pw.S, pw.stride_h, pw.stride_w, pw.pad_top, pw.pad_left, pw.num_segments = k, 1, 2, 2, 0, 0, 1
+        sg = pw.seg[0]
+        sg.x, sg.dy = self.stem_in.data_ptr(), dy.data_ptr()
+        sg.N, sg.H, sg.W, sg.Cin, sg.Ho, sg.Wo, sg.Cout = B, self.Hp, self.Wp, 32, dy.shape[1], dy.shape[2], c["cout"]
+        sg.x_pix_stride = 4
+        wsw = torch.empty((max(lib.rn_wgrad_workspace_bytes(ctypes.byref(pw)), 256),), dtype=torch.uint8,
+                          device=self.dev)
+        dwp = torch.zeros((c["cout"], k, 8, 4), dtype=torch.float32, device=self.dev)
+        gview = self._pview(self._kvar(op), self.G).view(c["cout"], k, k, 3)
+        self._keep += [pw, wsw, dwp]
+
+        def stem_bwd(st, bn_bwd=bn_bwd.run):
+            bn_bwd(st)
+            _C.check(lib.rn_conv2d_nhwc_wgrad(ctypes.byref(pw), dwp.data_ptr(), 0.0, wsw.data_ptr(),
+                                              wsw.numel(), st), "stem wgrad")
+            gview.copy_(dwp[:, :, :k, :3])   # [co][r][8 taps x 4 ch] -> [co][r][s][c]
+        self.bwd_steps.append(BackwardStep(stem_bwd, writes=[self._kvar(op)] + bn_bwd.writes))
+
+    def _topdown_din(self, op, l, joins):
+        """Gradient buffer of input l of top-down op `op`.  The level kernels overwrite it — except where the level passes
+        through (the top one: outs[l] IS ins[l]): there dout and din are one buffer, which the step updates in place on top
+        of what the readers of the output have written."""
+        name = op["ins"][l]
+        if name != op["outs"][l]:
+            return joins.sole(name, "topdown")
+        din, accumulate = joins.add(name, "topdown", balanced=False)
+        if not accumulate:
+            raise RuntimeError(f"top-down level {name} passes through, and no reader of it has written its gradient")
+        return din
+
+    def _plan_topdown_backward(self, op, joins):
+        lib, B = self.lib, self.B
+        L = len(op["ins"])
+        if op["act"] == "swish":
+            # rn_fpn_topdown_bwd_level refuses it: swish' needs the sum in front of the activation, and the
+            # forward pass keeps only its output
+            raise NotImplementedError(f"backward of the top-down op {op['outs'][0]} .. {op['outs'][-1]} with "
+                                      "activation 'swish' is not built (relu / relu6 / none are)")
+        act = _C.ACT_IDS[op["act"]]
+        if op.get("fusion"):
+            self._plan_fused_topdown_backward(op, act, joins)
+            return
+        prev = None
+        for l in range(L):
+            dout = self.grad[op["outs"][l]]
+            din = self._topdown_din(op, l, joins)
+            outp = self.t[op["outs"][l]].data_ptr() if l < L - 1 else None
+            a = (dout.data_ptr(), prev, outp, din.data_ptr(), B, dout.shape[1], dout.shape[2], dout.shape[3],
+                 act if l < L - 1 else _C.RN_ACT_NONE)
+            self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_fpn_topdown_bwd_level(*a, st),
+                                                                        "topdown_bwd")))
+            prev = din.data_ptr()
+
+    def _plan_balance_backward(self, op, joins):
+        lib, B = self.lib, self.B
+        names = op["tensors"]
+        dout = [self.grad["bal:" + n] for n in names]
+        ins = [self.t[n] for n in names]
+        din = [joins.sole(n, "balance") for n in names]
+        nsc = lib.rn_balance_features_bwd_scratch_bytes(len(names), op["mid"], B, ins[0].shape[1], ins[0].shape[2],
+                                                        ins[0].shape[3])
+        scratch = torch.empty((max(int(nsc), 256),), dtype=torch.uint8, device=self.dev)
+        pd, pi, pn = _C.ptr_array(dout), _C.ptr_array(ins), _C.ptr_array(din)
+        self._keep += [pd, pi, pn, scratch]
+        a = (pd, pi, pn, self.bal_avg.data_ptr(), scratch.data_ptr(), scratch.numel(), len(names), op["mid"], B,
+             ins[0].shape[1], ins[0].shape[2], ins[0].shape[3])
+        self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_balance_features_bwd(*a, st), "balance_bwd")))
+
+    def _plan_fused_topdown_backward(self, op, act, joins):
         """Backward of a weighted top-down op, finest level first: per level one rn_fpn_fused_bwd_level (the gated gradient
         g overwrites dout — nothing reads dout afterwards —, din, stage 1 of the two weight-gradient sums) and one
         rn_fpn_fused_bwd_finalize that writes dw_lower / dw_upper into the gradient arena.  Both run on the main stream, in
@@ -1265,8 +1311,7 @@ class TrainEngine:
         L = len(op["ins"])
         prev_g = prev_coef = None
         for l in range(L):
-            dout, din = self.grad[op["outs"][l]], self.grad[op["ins"][l]]
-            mark(op["ins"][l])
+            dout, din = self.grad[op["outs"][l]], self._topdown_din(op, l, joins)
             _, H, W, C = dout.shape
             if l == L - 1:
                 a = (dout.data_ptr(), prev_g, prev_coef, None, None, None, None, None, din.data_ptr(), None, 0, B, H, W, C,
@@ -1295,7 +1340,7 @@ class TrainEngine:
             prev_g, prev_coef = dout.data_ptr(), coef
 
     def set_wgrad_cap(self, on):
-        """The CU cap of the weight-gradient launches (see _plan_conv_backward) on / off: with the chip to themselves
+        """The CU cap of the weight-gradient launches (see _plan_wgrad) on / off: with the chip to themselves
         (bench.py's one-stream `exclusive` step) they run uncapped; the workspaces fit either split-K plan."""
         for p, cap in self._wgrad_capped:
             p.opts.wgrad_target_blocks = cap if on else 0
@@ -1440,155 +1485,174 @@ class TrainEngine:
                 launches.append([op])
         return launches
 
-    def _plan_conv_backward(self, ops, mark):
+    def _plan_bn_backward(self, ops, joins, *, profiled=True, steps=None):
+        """BatchNorm head of the backward of the launch over `ops` (BnGroup bn_groups[ops[0]["out"]]): dz of every segment
+        is the gradient at the layer's output, a residual input that needs a gradient gets it from the same pass (dres),
+        and one frozen or live BatchNorm step joins `steps` (default: bwd_steps).  Returns {op out: dy}, the gradients at
+        the conv outputs that the step writes."""
+        grp = self.bn_groups[ops[0]["out"]]
+        pb = grp.problem
+        for i, op in enumerate(ops):
+            s = pb.seg[i]
+            s.dz = self.grad[op["out"]].data_ptr()
+            if op.get("residual") and self.requires.get(op["residual"]):
+                dres, accumulate = joins.add(op["residual"], "bn:" + ops[0]["out"], balanced=False)
+                s.dres, s.dres_accumulate = dres.data_ptr(), int(accumulate)
+        if grp.frozen:
+            step = self._bn_frozen_bwd_step(grp)
+        else:   # (ws: stage 1 already written there by the dgrad launch that produced dz)
+            step = self._bn_bwd_step(grp, self.bn_bwd_ws.get(id(pb), grp.ws), profiled)
+        (self.bwd_steps if steps is None else steps).append(step)
+        return {op["out"]: grp.dys[i] for i, op in enumerate(ops)}
+
+    def _plan_plain_dy(self, ops):
+        """{op out: dy} of convs without a BatchNorm: the prediction convs' dy is the buffer the loss gradient is written to,
+        the others' comes out of an rn_act_bwd step."""
+        lib = self.lib
+        dy_of = {}
+        for op in ops:
+            if op["out_dtype"] == "f32":      # prediction convs: loss gradient arrives in fp32
+                shp = list(self.t[op["out"]].shape)
+                shp[3] = (shp[3] + 63) // 64 * 64     # K dimension of the dgrad GEMM: pad 36/720 -> 64/768
+                dyb = torch.zeros(shp, dtype=self.h16, device=self.dev)
+                dy_of[op["out"]] = dyb
+            else:
+                if op["act"] == "swish":     # rn_act_bwd refuses it: swish' is no function of the stored output
+                    raise NotImplementedError(f"backward of the conv op {op['out']} ({op['conv']}): activation "
+                                              "'swish' without a BatchNorm in front is not built")
+                dyb = torch.empty_like(self.t[op["out"]])
+                dy_of[op["out"]] = dyb
+                a = (self.grad[op["out"]].data_ptr(), self.t[op["out"]].data_ptr(), dyb.data_ptr(),
+                     dyb.numel(), _C.ACT_IDS[op["act"]])
+                self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_act_bwd(*a, st), "rn_act_bwd")))
+        self._keep += list(dy_of.values())
+        return dy_of
+
+    def _plan_wgrad(self, cname, cops, dy_of):
+        """Weight gradient of conv layer `cname`, one launch over the ops `cops` that share it"""
         lib, B = self.lib, self.B
+        c = self.g.convs[cname]
+        kvar = c.get("kvar", cname + "/kernel")
+        p = _C.WgradProblem()
+        p.opts = self.launch_opts
+        p.R = p.S = c["k"]
+        p.stride_h = p.stride_w = c["stride"]
+        p.pad_top = p.pad_left = cops[0]["pad"]
+        p.num_segments = len(cops)
+        # rn_conv2d_nhwc_wgrad takes Cout % 4 == 0: the auxiliary head's 9-channel prediction conv runs as 12 (dy's pad
+        # channels are zero, so rows 9 - 11 of dw are) into a buffer of its own, the live rows are copied to the arena
+        cout4 = -(-c["cout"] // 4) * 4
+        for i, op in enumerate(cops):
+            x, dy = self._src(op["inp"]), dy_of[op["out"]]
+            s = p.seg[i]
+            s.x, s.dy = x.data_ptr(), dy.data_ptr()
+            s.N, s.H, s.W, s.Cin, s.Ho, s.Wo, s.Cout = B, x.shape[1], x.shape[2], c["cin"], dy.shape[1], dy.shape[2], cout4
+            s.dy_pix_stride = dy.shape[3]
+        # Two-stream backward: a weight-gradient launch is capped to ~2/3 of the CUs (rn_launch_opts.wgrad_target_blocks).
+        # Its persistent workgroups own a CU for hundreds of microseconds; when they cover the whole chip every
+        # main-stream launch — the critical path — queues behind them.  Measured in one process (tools/ab_step.py):
+        # 31.40 -> 30.48 ms and 32.45 -> 31.34 ms per step on two boxes with 176 workgroups for the 256-wide kernels
+        # and 256 (two per CU) for the 128-tile kernel; 128 / 192 is already slower again.  RNET_WGRAD_CUS=0: no cap.
+        if self._wgrad_cap and not p.opts.wgrad_target_blocks:
+            kid = lib.rn_wgrad_kernel_id(ctypes.byref(p))
+            p.opts.wgrad_target_blocks = self._wgrad_cap[0] if kid in (1, 2) else self._wgrad_cap[1]
+            self._wgrad_capped.append((p, int(p.opts.wgrad_target_blocks)))
+        ws = self._wgrad_workspace([p], lambda: lib.rn_wgrad_workspace_bytes(ctypes.byref(p)))
+        dw = self._pview(kvar, self.G)
+        dw_live = None
+        if cout4 != c["cout"]:
+            dw_live, dw = dw, torch.zeros((cout4 * c["k"] * c["k"] * c["cin"],), dtype=torch.float32, device=self.dev)
+            self._keep.append(dw)
+        self._keep += [p, ws]
+        self.wgrad_launches.append(("wgrad:" + cname, p))
+        # algorithmic FLOPs of the layer's weight gradient: 2 * pixels * k*k * Cin * Cout over the segments
+        flw = sum(2 * B * p.seg[i].Ho * p.seg[i].Wo * c["k"] * c["k"] * c["cin"] * c["cout"] for i in range(len(cops)))
+        # (a layer with a buffer of its own stays out of _group_wgrad_steps' merge of same-shape layers)
+        step = self._wgrad_step(lib.rn_conv2d_nhwc_wgrad, (ctypes.byref(p), dw.data_ptr(), 0.0, ws.data_ptr(), ws.numel()),
+                                "rn_conv2d_nhwc_wgrad", flw, self._wgrad_bytes(p),
+                                self._wgrad_kernel_name(p) + " + wgrad_reduce_kernel", "wgrad:" + cname, [kvar],
+                                item=(p, dw, ws, flw) if dw_live is None else None)
+        if dw_live is not None:
+            def padded_wgrad(st, wgrad=step.run, src=dw, dst=dw_live):
+                wgrad(st)
+                _C.check(lib.rn_reduce_rows_f32(_C.ptr(src), 1, dst.numel(), dst.numel(), 0.0, _C.ptr(dst), st),
+                         "live rows of a padded weight gradient")
+            step = BackwardStep(padded_wgrad, side=True, writes=step.writes)
+        self.bwd_steps.append(step)
+
+    def _plan_bias_grad(self, cname, cops, ops, dy_of, grp):
+        """Bias gradient of conv layer `cname` = column sums of dy over every segment (two-stage reduction kernel).
+        ops: the launch `cops` belong to; grp: its BnGroup when the BatchNorm behind it trains, else None."""
+        lib = self.lib
+        pb2 = _C.BnProblem()
+        pb2.num_segments, pb2.act, pb2.bessel, pb2.eps, pb2.momentum, pb2.count_scale = len(cops), 0, 0, 0.0, 0.0, 1.0
+        cw = dy_of[cops[0]["out"]].shape[3]    # channel width of dy (padded for prediction convs)
+        bs = torch.zeros((len(cops), 2, cw), dtype=torch.float32, device=self.dev)
+        for i, op in enumerate(cops):
+            dy = dy_of[op["out"]]
+            s = pb2.seg[i]
+            s.y, s.sums = dy.data_ptr(), bs[i].data_ptr()
+            s.P, s.C = dy.shape[0] * dy.shape[1] * dy.shape[2], cw
+        # A conv in front of a live BatchNorm: its dy is written by rn_bn_bwd_apply, which can sum the columns of
+        # what it stores on the way out (rn_bn_segment.dy_colsum_partial) — stage 1 of this reduction then never
+        # reads the dy tensor again (FPN + head-tower convs: 17 launches, ~1 ms of side-stream HBM reads per step;
+        # same-process A/B of the step with / without ANY bias-gradient launch: 29.73 / 29.50 ms).  Where
+        # rn_bn_bwd_colsum_chunks refuses a segment, and in front of a frozen BatchNorm (rn_bn_frozen_bwd has no
+        # such epilogue), the separate pass stays.
+        fused_cs = False
+        if grp is not None:
+            pb = grp.problem
+            seg_of = [ops.index(op) for op in cops]
+            chunks = [lib.rn_bn_bwd_colsum_chunks(ctypes.byref(pb), j) for j in seg_of]
+            if all(ch > 0 for ch in chunks):
+                fused_cs = True
+                for i, ch in enumerate(chunks):
+                    pb2.seg[i].ext_chunks = ch
+        ws2 = torch.zeros((max(lib.rn_bn_workspace_bytes(ctypes.byref(pb2)), 256),), dtype=torch.uint8,
+                          device=self.dev)
+        if fused_cs:
+            for i, j in enumerate(seg_of):
+                pb.seg[j].dy_colsum_partial = ws2.data_ptr() + lib.rn_bn_partial_offset_bytes(ctypes.byref(pb2), i)
+        db = self._pview(cname + "/bias", self.G)
+        self._keep += [pb2, bs, ws2]
+
+        def bias_grad(st, pr=ctypes.byref(pb2), n=self.g.convs[cname]["cout"], rows=len(cops), stride=2 * cw):
+            _C.check(lib.rn_bn_stats(pr, _C.ptr(ws2), ws2.numel(), st), "bias colsum")
+            # sum of the per-level column sums (row 0 of every [2][cw] block), levels in order
+            _C.check(lib.rn_reduce_rows_f32(_C.ptr(bs), rows, stride, n, 0.0, _C.ptr(db), st), "bias grad")
+        self.bwd_steps.append(BackwardStep(bias_grad, side=True, writes=[cname + "/bias"]))
+
+    def _plan_conv_backward(self, ops, joins):
+        """Backward of the conv launch over `ops`: gradient at the conv outputs (through the BatchNorm, or plain), weight and
+        bias gradient of every distinct (shared) conv layer, data gradients."""
         if not self._conv_trainable(ops[0]) and not any(self.requires.get(o["inp"]) for o in ops):
             return
         if not self._conv_trainable(ops[0]):
             raise NotImplementedError("backward through a frozen conv that sits above trainable layers")
         live_bn = bool(self._bn_trainable(ops[0]))
-        frozen_bn = self._bn_frozen(ops[0])
-        # (a) gradient wrt the conv output
-        if live_bn or frozen_bn:
-            grp = self.bn_groups[ops[0]["out"]]
-            pb = grp.problem
-            for i, op in enumerate(ops):
-                s = pb.seg[i]
-                s.dz = self.grad[op["out"]].data_ptr()
-                if op.get("residual") and self.requires.get(op["residual"]):
-                    dres, first = self._grad_target(op["residual"], mark, balanced=False)
-                    s.dres, s.dres_accumulate = dres.data_ptr(), 0 if first else 1
-            if frozen_bn:
-                self.bwd_steps.append(self._bn_frozen_bwd_step(grp))
-            else:   # (ws: stage 1 already written there by the dgrad launch that produced dz)
-                self.bwd_steps.append(self._bn_bwd_step(grp, self.bn_bwd_ws.get(id(pb), grp.ws)))
-            dy_of = {op["out"]: grp.dys[i] for i, op in enumerate(ops)}
+        if live_bn or self._bn_frozen(ops[0]):
+            dy_of = self._plan_bn_backward(ops, joins)
         else:
-            dy_of = {}
-            for op in ops:
-                if op["out_dtype"] == "f32":      # prediction convs: loss gradient arrives in fp32
-                    shp = list(self.t[op["out"]].shape)
-                    shp[3] = (shp[3] + 63) // 64 * 64     # K dimension of the dgrad GEMM: pad 36/720 -> 64/768
-                    dyb = torch.zeros(shp, dtype=self.h16, device=self.dev)
-                    dy_of[op["out"]] = dyb
-                else:
-                    if op["act"] == "swish":     # rn_act_bwd refuses it: swish' is no function of the stored output
-                        raise NotImplementedError(f"backward of the conv op {op['out']} ({op['conv']}): activation "
-                                                  "'swish' without a BatchNorm in front is not built")
-                    dyb = torch.empty_like(self.t[op["out"]])
-                    dy_of[op["out"]] = dyb
-                    a = (self.grad[op["out"]].data_ptr(), self.t[op["out"]].data_ptr(), dyb.data_ptr(),
-                         dyb.numel(), _C.ACT_IDS[op["act"]])
-                    self.bwd_steps.append(BackwardStep(lambda st, a=a: _C.check(lib.rn_act_bwd(*a, st), "rn_act_bwd")))
-            self._keep += list(dy_of.values())
+            dy_of = self._plan_plain_dy(ops)
         self.dy_of.update(dy_of)
-        # (b) weight / bias gradients, one problem per distinct (shared) conv layer
         by_conv = {}
         for op in ops:
             by_conv.setdefault(op["conv"], []).append(op)
         for cname, cops in by_conv.items():
-            c = self.g.convs[cname]
-            kvar = c.get("kvar", cname + "/kernel")
-            p = _C.WgradProblem()
-            p.opts = self.launch_opts
-            p.R = p.S = c["k"]
-            p.stride_h = p.stride_w = c["stride"]
-            p.pad_top = p.pad_left = cops[0]["pad"]
-            p.num_segments = len(cops)
-            # rn_conv2d_nhwc_wgrad takes Cout % 4 == 0: the auxiliary head's 9-channel prediction conv runs as 12 (dy's pad
-            # channels are zero, so rows 9 - 11 of dw are) into a buffer of its own, the live rows are copied to the arena
-            cout4 = -(-c["cout"] // 4) * 4
-            for i, op in enumerate(cops):
-                x, dy = self._src(op["inp"]), dy_of[op["out"]]
-                s = p.seg[i]
-                s.x, s.dy = x.data_ptr(), dy.data_ptr()
-                s.N, s.H, s.W, s.Cin, s.Ho, s.Wo, s.Cout = B, x.shape[1], x.shape[2], c["cin"], dy.shape[1], dy.shape[2], cout4
-                s.dy_pix_stride = dy.shape[3]
-            # Two-stream backward: a weight-gradient launch is capped to ~2/3 of the CUs (rn_launch_opts.wgrad_target_blocks).
-            # Its persistent workgroups own a CU for hundreds of microseconds; when they cover the whole chip every
-            # main-stream launch — the critical path — queues behind them.  Measured in one process (tools/ab_step.py):
-            # 31.40 -> 30.48 ms and 32.45 -> 31.34 ms per step on two boxes with 176 workgroups for the 256-wide kernels
-            # and 256 (two per CU) for the 128-tile kernel; 128 / 192 is already slower again.  RNET_WGRAD_CUS=0: no cap.
-            if self._wgrad_cap and not p.opts.wgrad_target_blocks:
-                kid = lib.rn_wgrad_kernel_id(ctypes.byref(p))
-                p.opts.wgrad_target_blocks = self._wgrad_cap[0] if kid in (1, 2) else self._wgrad_cap[1]
-                self._wgrad_capped.append((p, int(p.opts.wgrad_target_blocks)))
-            ws = self._wgrad_workspace([p], lambda: lib.rn_wgrad_workspace_bytes(ctypes.byref(p)))
-            dw = self._pview(kvar, self.G)
-            dw_live = None
-            if cout4 != c["cout"]:
-                dw_live, dw = dw, torch.zeros((cout4 * c["k"] * c["k"] * c["cin"],), dtype=torch.float32, device=self.dev)
-                self._keep.append(dw)
-            self._keep += [p, ws]
-            self.wgrad_launches.append(("wgrad:" + cname, p))
-            # algorithmic FLOPs of the layer's weight gradient: 2 * pixels * k*k * Cin * Cout over the segments
-            flw = sum(2 * B * p.seg[i].Ho * p.seg[i].Wo * c["k"] * c["k"] * c["cin"] * c["cout"] for i in range(len(cops)))
-            # (a layer with a buffer of its own stays out of _group_wgrad_steps' merge of same-shape layers)
-            step = self._wgrad_step(lib.rn_conv2d_nhwc_wgrad, (ctypes.byref(p), dw.data_ptr(), 0.0, ws.data_ptr(), ws.numel()),
-                                    "rn_conv2d_nhwc_wgrad", flw, self._wgrad_bytes(p),
-                                    self._wgrad_kernel_name(p) + " + wgrad_reduce_kernel", "wgrad:" + cname, [kvar],
-                                    item=(p, dw, ws, flw) if dw_live is None else None)
-            if dw_live is not None:
-                def padded_wgrad(st, wgrad=step.run, src=dw, dst=dw_live):
-                    wgrad(st)
-                    _C.check(lib.rn_reduce_rows_f32(_C.ptr(src), 1, dst.numel(), dst.numel(), 0.0, _C.ptr(dst), st),
-                             "live rows of a padded weight gradient")
-                step = BackwardStep(padded_wgrad, side=True, writes=step.writes)
-            self.bwd_steps.append(step)
-            if c["bias"]:
-                # bias gradient = column sums of dy over every segment (two-stage reduction kernel)
-                pb2 = _C.BnProblem()
-                pb2.num_segments, pb2.act, pb2.bessel, pb2.eps, pb2.momentum, pb2.count_scale = len(cops), 0, 0, 0.0, 0.0, 1.0
-                cw = dy_of[cops[0]["out"]].shape[3]    # channel width of dy (padded for prediction convs)
-                bs = torch.zeros((len(cops), 2, cw), dtype=torch.float32, device=self.dev)
-                for i, op in enumerate(cops):
-                    dy = dy_of[op["out"]]
-                    s = pb2.seg[i]
-                    s.y, s.sums = dy.data_ptr(), bs[i].data_ptr()
-                    s.P, s.C = dy.shape[0] * dy.shape[1] * dy.shape[2], cw
-                # A conv in front of a live BatchNorm: its dy is written by rn_bn_bwd_apply, which can sum the columns of
-                # what it stores on the way out (rn_bn_segment.dy_colsum_partial) — stage 1 of this reduction then never
-                # reads the dy tensor again (FPN + head-tower convs: 17 launches, ~1 ms of side-stream HBM reads per step;
-                # same-process A/B of the step with / without ANY bias-gradient launch: 29.73 / 29.50 ms).  Where
-                # rn_bn_bwd_colsum_chunks refuses a segment, and in front of a frozen BatchNorm (rn_bn_frozen_bwd has no
-                # such epilogue), the separate pass stays.
-                fused_cs = False
-                if live_bn:
-                    seg_of = [ops.index(op) for op in cops]
-                    chunks = [lib.rn_bn_bwd_colsum_chunks(ctypes.byref(pb), j) for j in seg_of]
-                    if all(ch > 0 for ch in chunks):
-                        fused_cs = True
-                        for i, ch in enumerate(chunks):
-                            pb2.seg[i].ext_chunks = ch
-                ws2 = torch.zeros((max(lib.rn_bn_workspace_bytes(ctypes.byref(pb2)), 256),), dtype=torch.uint8,
-                                  device=self.dev)
-                if fused_cs:
-                    for i, j in enumerate(seg_of):
-                        pb.seg[j].dy_colsum_partial = ws2.data_ptr() + lib.rn_bn_partial_offset_bytes(ctypes.byref(pb2), i)
-                db = self._pview(cname + "/bias", self.G)
-                self._keep += [pb2, bs, ws2]
-
-                def bias_grad(st, pr=ctypes.byref(pb2), ws2=ws2, bs=bs, db=db, n=c["cout"], rows=len(cops), stride=2 * cw):
-                    _C.check(lib.rn_bn_stats(pr, _C.ptr(ws2), ws2.numel(), st), "bias colsum")
-                    # sum of the per-level column sums (row 0 of every [2][cw] block), levels in order
-                    _C.check(lib.rn_reduce_rows_f32(_C.ptr(bs), rows, stride, n, 0.0, _C.ptr(db), st), "bias grad")
-                self.bwd_steps.append(BackwardStep(bias_grad, side=True, writes=[cname + "/bias"]))
-        # (c) data gradients
+            self._plan_wgrad(cname, cops, dy_of)
+            if self.g.convs[cname]["bias"]:
+                self._plan_bias_grad(cname, cops, ops, dy_of, self.bn_groups[ops[0]["out"]] if live_bn else None)
         packs = {}
         for sub in self._distinct_inputs([op for op in ops if self.requires.get(op["inp"])]):
-            self._plan_dgrad_launch(sub, dy_of, mark, packs)
+            self._plan_dgrad_launch(sub, dy_of, joins, packs)
 
-    def _plan_dw_backward(self, ops, mark):
+    def _plan_dw_backward(self, ops, joins):
         """depthwise conv (+BN+act) backward: BN backward -> dy; weight gradient (summed over the levels of a
         shared separable conv); data gradient = the forward kernel on (zero-upsampled) dy with the
         tap-reversed filter, accumulating into gradient buffers that already hold a contribution."""
         lib, B = self.lib, self.B
         if self._bn_trainable(ops[0]) or self._bn_frozen(ops[0]):
-            grp = self.bn_groups[ops[0]["out"]]
-            for i, op in enumerate(ops):
-                grp.problem.seg[i].dz = self.grad[op["out"]].data_ptr()
-            self.bwd_steps.append(self._bn_frozen_bwd_step(grp) if grp.frozen else self._bn_bwd_step(grp, grp.ws))
-            dy_of = {op["out"]: grp.dys[i] for i, op in enumerate(ops)}
+            dy_of = self._plan_bn_backward(ops, joins)
         else:
             dy_of = {op["out"]: self.grad[op["out"]] for op in ops}
         by_layer = {}
@@ -1620,6 +1684,7 @@ class TrainEngine:
             p = _C.DwProblem()
             p.k, p.stride, p.act, p.num_segments = k, 1, 0, len(sub)
             p.pad_top, p.pad_left = k - 1 - sub[0]["pad_top"], k - 1 - sub[0]["pad_left"]
+            name = "dw_dgrad:" + "+".join(o["out"] for o in sub)
             ups = []
             for i, op in enumerate(sub):
                 d = self.g.dws[op["dw"]]
@@ -1632,22 +1697,17 @@ class TrainEngine:
                 x = self._src(op["inp"])
                 H, W = x.shape[1], x.shape[2]
                 if stride == 2:
-                    src, up_args = self._zero_upsampled(src, H, W)
-                    ups.append(up_args)
-                gbuf, first = self._grad_target(op["inp"], mark)
+                    src = self._zero_upsampled(src, H, W, ups)
+                gbuf, accumulate = joins.add(op["inp"], name)
                 s = p.seg[i]
                 s.x, s.w, s.y = src.data_ptr(), flips[op["dw"]].data_ptr(), gbuf.data_ptr()
                 s.scale, s.shift = None, None
-                s.residual = None if first else gbuf.data_ptr()
+                s.residual = gbuf.data_ptr() if accumulate else None
                 s.N, s.H, s.W, s.C, s.Ho, s.Wo = B, H, W, d["C"], H, W
             self._keep.append(p)
-            self.dw_launches.append(("dw_dgrad:" + "+".join(o["out"] for o in sub), "dgrad", p, ups))
-
-            def dgrad(st, p=p, ups=ups):
-                for u in ups:
-                    _C.check(lib.rn_upsample_zero2x(*u, st), "rn_upsample_zero2x")
-                _C.check(lib.rn_depthwise_conv2d_nhwc_fwd(ctypes.byref(p), st), "dw dgrad")
-            self.bwd_steps.append(BackwardStep(dgrad))
+            self.dw_launches.append((name, "dgrad", p, ups))
+            self.bwd_steps.append(self._dgrad_step(ups, functools.partial(lib.rn_depthwise_conv2d_nhwc_fwd, ctypes.byref(p)),
+                                                   what="dw dgrad"))
 
     def _bn_bwd_fusable(self, name):
         """(rn_bn_problem, segment) of the BatchNorm + ReLU layer that produced `name` when stage 1 of its backward
@@ -1708,7 +1768,7 @@ class TrainEngine:
                     self._algo[id(cp)] = (fl0, by0 + y_bytes)
         return added
 
-    def _plan_dgrad_launch(self, need, dy_of, mark, packs):
+    def _plan_dgrad_launch(self, need, dy_of, joins, packs):
         """One data-gradient launch over the ops `need` (distinct inputs): the forward implicit-GEMM kernel on dy with the
         flipped / transposed weights, in one of three forms chosen per launch."""
         lib, B = self.lib, self.B
@@ -1732,9 +1792,10 @@ class TrainEngine:
         p.stride_h = p.stride_w = 1
         p.pad_top = p.pad_left = 0 if subpixel else k - 1 - pad
         p.act, p.out_dtype, p.num_segments = _C.RN_ACT_NONE, _C.RN_DT_BF16, len(need)
-        ups, post, firsts = [], [], []   # rn_upsample_zero2x before the launch; per-segment arguments of the form's post-op
+        ups, post, joined = [], [], False   # rn_upsample_zero2x before the launch; per-segment arguments of the form's post-op
         post_op = ((lib.rn_depth_to_space2x, "rn_depth_to_space2x") if subpixel else
                    (lib.rn_scatter_add2x, "rn_scatter_add2x") if lowres else None)
+        name = "dgrad:" + (need[0].get("group") or need[0]["out"])
         fl = by = 0
         for i, op in enumerate(need):
             c = self.g.convs[op["conv"]]
@@ -1750,22 +1811,21 @@ class TrainEngine:
                                          1 if subpixel else 0))
             x = self._src(op["inp"])
             H, W = x.shape[1], x.shape[2]
-            gbuf, first = self._grad_target(op["inp"], mark)
-            firsts.append(first)
+            gbuf, accumulate = joins.add(op["inp"], name)
+            joined = joined or accumulate
             # what the forms differ in: source, destination, output channels, residual, post-op arguments
             src, dst, cout, res = dy, gbuf, cin, None
             if subpixel:
                 cout = 4 * cin
                 dst = torch.empty((B, dy.shape[1], dy.shape[2], cout), dtype=self.h16, device=self.dev)
-                post.append((dst.data_ptr(), gbuf.data_ptr(), B, dy.shape[1], dy.shape[2], cin, 0 if first else 1))
+                post.append((dst.data_ptr(), gbuf.data_ptr(), B, dy.shape[1], dy.shape[2], cin, int(accumulate)))
             elif lowres:
                 dst = torch.empty((B, dy.shape[1], dy.shape[2], cin), dtype=self.h16, device=self.dev)
-                post.append((dst.data_ptr(), gbuf.data_ptr(), B, dy.shape[1], dy.shape[2], cin, H, W, 0 if first else 1))
+                post.append((dst.data_ptr(), gbuf.data_ptr(), B, dy.shape[1], dy.shape[2], cin, H, W, int(accumulate)))
             else:
                 if stride == 2:
-                    src, up_args = self._zero_upsampled(dy, H, W)
-                    ups.append(up_args)
-                res = None if first else gbuf.data_ptr()
+                    src = self._zero_upsampled(dy, H, W, ups)
+                res = gbuf.data_ptr() if accumulate else None
             if dst is not gbuf:
                 self._keep.append(dst)
             s = p.seg[i]
@@ -1778,19 +1838,17 @@ class TrainEngine:
             fl += 2 * B * Ho * Wo * k * k * cin * c["cout"]
             by += 2 * B * Ho * Wo * c["cout"] + 2 * B * H * W * cin * (2 if res else 1) + 2 * k * k * cin * c["cout"]
         # the BatchNorm-backward epilogue takes dz as it leaves the GEMM: the plain stride-1 form, first writer everywhere
-        if post_op is None and stride == 1 and all(firsts):
+        if post_op is None and stride == 1 and not joined:
             by += self._fuse_bn_bwd(p, need)
         self._algo[id(p)] = (fl, by)
         self._keep.append(p)
-        self.conv_launches.append(("dgrad:" + (need[0].get("group") or need[0]["out"]), p))
+        self.conv_launches.append((name, p))
+        self.bwd_steps.append(self._dgrad_step(ups, functools.partial(self._launch_conv, p, what="dgrad"), post_op, post))
 
-        def dgrad(st, p=p, ups=ups, post=post):
-            for u in ups:
-                _C.check(lib.rn_upsample_zero2x(*u, st), "rn_upsample_zero2x")
-            self._launch_conv(p, st, "dgrad")
-            for a in post:
-                _C.check(post_op[0](*a, st), post_op[1])
-        self.bwd_steps.append(BackwardStep(dgrad))
+    # op kind -> planner(self, the op or the ops of its launch, joins) of its backward steps (_build_backward)
+    _backward_planners = {"conv": _plan_conv_backward, "dwconv": _plan_dw_backward, "se": _plan_se_backward,
+                          "maxpool": _plan_maxpool_backward, "stem": _plan_stem_backward,
+                          "topdown": _plan_topdown_backward, "balance": _plan_balance_backward}
 
     # ---- one training step -----------------------------------------------------------------------------
     def refresh_dgrad_weights(self, st):

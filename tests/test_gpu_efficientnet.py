@@ -664,3 +664,27 @@ def test_config4_bench_batch_backward_is_stream_and_run_independent(cuda):
     assert int((grads[0] != 0).sum()) > grads[0].numel() // 2
     assert torch.equal(grads[0], grads[1]), "two-stream gradients differ from the one-stream order"
     assert torch.equal(grads[0], grads[2]), "two runs of the two-stream order differ"
+
+
+def test_gradient_joins_match_the_graph(cuda):
+    """Build only.  EfficientNet-B0 256^2, batch 2, with its depthwise, squeeze-excite and drop_connect layers: the
+    planner's record of who writes every activation-gradient buffer (engine.joins.writers) against the count of readers
+    taken from the graph alone (join_counts.py) — no contribution lost, none doubled, and the overwriting steps
+    (squeeze-excite, top-down) first."""
+    from join_counts import check_joins
+    from retinanet.cfg import efficientnet_params
+    from retinanet.model import ModelBuilder
+    from retinanet.model.train_engine import TrainEngine
+    p = efficientnet_params("efficientnet-b0", input_size=256)
+    p.architecture.batch_norm.use_sync = False
+    eng = TrainEngine(ModelBuilder(p, "train", device=cuda, seed=5)(), 2, frozen_regexes=[])
+    assert len(eng.dc_masks) == 9 and eng.dw_launches
+    want = check_joins(eng)
+    writers = eng.joins.writers
+    ses = [o for o in eng.ops if o["op"] == "se"]
+    assert len(ses) == 16
+    for o in ses:   # the gated tensor has the squeeze-excite step as its only reader, the step's output the project conv
+        assert writers[o["inp"]] == ["se:" + o["out"]] and len(writers[o["out"]]) == 1, (o["inp"], writers[o["inp"]])
+    skips = {o["residual"] for o in eng.ops if o.get("residual")}
+    assert len(skips) == 9 and all(want[n] >= 2 and writers[n][0].startswith("bn:") for n in skips)
+    assert any(s.startswith("dw_dgrad:") for labels in writers.values() for s in labels[1:])   # a depthwise launch accumulates

@@ -657,3 +657,18 @@ def test_train_step_moves_and_decays_the_fusion_weights(cuda, tmp_path, mode):
         for arena in ("P", "V", "E"):
             assert torch.equal(eng2._pview(k, getattr(eng2, arena)), eng._pview(k, getattr(eng, arena))), (k, arena)
         assert torch.equal(model2.variables[k].reshape(-1), eng._pview(k))
+
+
+def test_gradient_joins_match_the_graph(cuda):
+    """Build only.  The fast_attention engine at batch 2: the planner's record of who writes every activation-gradient
+    buffer (engine.joins.writers) against the count of readers taken from the graph alone (join_counts.py).  The weighted
+    top-down backward overwrites din of every level below the top, so it must be the first writer of each; the top level
+    passes through, its gradient is updated in place behind the output conv's data gradient."""
+    from join_counts import check_joins
+    p, model, eng, targets, images = _setup(cuda, "fast_attention", 256, 2, True)
+    check_joins(eng)
+    top = next(o for o in eng.ops if o["op"] == "topdown")
+    assert top.get("fusion") and id(top) in eng.fusion_state and top["ins"][-1] == top["outs"][-1]
+    writers = eng.joins.writers
+    assert all(writers[n][0] == "topdown" and "topdown" not in writers[n][1:] for n in top["ins"][:-1])
+    assert writers[top["ins"][-1]][0].startswith("dgrad:") and writers[top["ins"][-1]][1:] == ["topdown"], writers[top["ins"][-1]]

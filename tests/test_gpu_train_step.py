@@ -421,3 +421,30 @@ def test_dynamic_loss_scale_is_applied_one_forward_pass_later(cuda):
     eng.finish_step()
     assert eng.step_count == n + 1 and eng.loss_scale["scale"] == 2 * s0 and eng.loss_scale["good"] == 0
     assert not torch.equal(eng.P, before)
+
+
+def test_gradient_joins_match_the_graph(cuda):
+    """Build only.  ResNet-50 128^2, batch 2, nothing frozen: the planner's record of who writes every activation-gradient
+    buffer (engine.joins.writers) against the count of readers taken from the graph alone (join_counts.py) — no
+    contribution lost, none doubled, and the overwriting steps (top-down, BalanceFeatures) first.  The bottleneck stages
+    give the joins: the input of an identity block is read by the block's first 1x1 conv and by the skip (two writers, the
+    first of them the BatchNorm backward's dres), a projection shortcut's output by the skip alone (one), and the last
+    output of stages 2 and 3 by the next stage's projection shortcut, its first 1x1 conv and the FPN lateral conv (three
+    data gradients)."""
+    from join_counts import check_joins
+    p, model, eng, targets, images = _setup(cuda, 128, 2, True, seed=7, depth=50, freeze=False)
+    want = check_joins(eng)
+    writers = eng.joins.writers
+    residual = {o["residual"] for o in eng.ops if o.get("residual")}
+    shortcuts = {n for n in residual if want[n] == 1}
+    assert len(residual) == 16 and len(shortcuts) == 4 and {want[n] for n in residual - shortcuts} == {2}
+    for n in residual:   # the skip's gradient comes out of the block's last BatchNorm backward, ahead of the data gradients
+        assert writers[n][0].startswith("bn:") and all(s.startswith("dgrad:") for s in writers[n][1:]), (n, writers[n])
+    three = [n for n in want if want[n] == 3]
+    assert max(want.values()) == 3 and len(three) == 2, three
+    assert all(s.startswith("dgrad:") for n in three for s in writers[n]) and not set(three) & residual
+    pool = next(o for o in eng.ops if o["op"] == "maxpool")
+    assert [s.split(":")[0] for s in writers[pool["out"]]] == ["dgrad", "dgrad"]     # projection shortcut + first 1x1 conv
+    assert writers[pool["inp"]] == ["maxpool:" + pool["out"]]
+    bal = eng.ops[[o["op"] for o in eng.ops].index("balance")]["tensors"]
+    assert len(bal) == 5 and all(writers[n] == ["balance"] and want["bal:" + n] == 2 for n in bal)   # both heads read the copy
