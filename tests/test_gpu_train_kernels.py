@@ -1078,14 +1078,7 @@ def _bn_bwd_f64(g, xhat, invstd, gamma):
     return dy, dgamma, dbeta
 
 
-def _ulp_outliers(got, want64, ulps=2.0):
-    """fraction of bf16 elements farther than `ulps` bf16 ulps from the float64 value (ulp of the element's own magnitude,
-    floored at 2^-8 of the tensor's rms: a sum that cancels to ~0 has the rounding of its terms, not of its value)"""
-    w = want64.abs()
-    rms = want64.pow(2).mean().sqrt()
-    mag = torch.maximum(w, rms * 2.0 ** -8)
-    ulp = torch.pow(2.0, torch.floor(torch.log2(mag)) - 7)
-    return ((got.double() - want64).abs() > ulps * ulp).double().mean().item()
+from ulp_ref import _ulp_outliers   # noqa: E402  (moved unchanged: the gradient-join tests share it)
 
 
 def test_bottleneck_tail_forward_backward_tight(cuda):
