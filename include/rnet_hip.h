@@ -570,7 +570,8 @@ typedef struct {
   int32_t bessel;        /* 1: moving variance uses the n/(n-1) corrected batch variance (fused BN) */
   float eps;
   float momentum;
-  float count_scale;     /* replicas contributing to `sums` (1 for local BN) */
+  float count_scale;     /* replicas contributing to `sums` (1 for local BN): n = P * count_scale in rn_bn_finalize and
+                          * rn_bn_bwd_apply.  A value <= 0 (a zero-filled descriptor) reads as 1. */
   rn_bn_segment seg[RN_CONV_MAX_SEGMENTS];
 } rn_bn_problem;
 
