@@ -190,6 +190,9 @@ int rn_topk_per_class(const float* scores, int B, int64_t A, int K, int top_k, f
  *      anchors); lists of up to 5120 candidates (every shipped configuration: 5000) run the one-step-per-
  *      selection kernel, longer ones the queue loop — the same selections and score bits either way
  *      (RN_EINVAL beyond 8192).  max_det <= 256, K * max_det <= 16384.
+ *      K <= 125: the compaction workgroup keeps the survivors of a sub-tile of 64 anchors x K classes in LDS, 8 bytes
+ *      each plus 8 bytes per class, within 64 KB (5/4 of a sub-tile up to K = 101, exactly one sub-tile for
+ *      K = 102 .. 125); RN_EINVAL from K = 126, checked on the host before anything is enqueued.
  */
 size_t rn_detect_workspace_bytes(int B, int64_t A, int K, int max_det);
 int rn_detect_per_class(const float* const* class_logits, const int64_t* level_offsets, int num_levels, int B,

@@ -1265,6 +1265,15 @@ extern "C" int rn_detect_per_class(const float* const* class_logits, const int64
     rn_set_error("rn_detect_per_class: workspace %zu < %zu", workspace_bytes, need);
     return RN_ENOMEM;
   }
+  int cap_list = RN_CT_ANCHORS * K + RN_CT_ANCHORS * K / 4;   // survivors' list: one sub-tile at worst + a quarter
+  size_t lds_ct = rn_align_up((size_t)cap_list * 8 + 4 + (size_t)K * 8 + 16, 16);
+  if (lds_ct > 64 * 1024) {   // K >= 102: exactly one sub-tile (every sub-tile with a survivor then flushes at once)
+    cap_list = RN_CT_ANCHORS * K;
+    lds_ct = rn_align_up((size_t)cap_list * 8 + 4 + (size_t)K * 8 + 16, 16);
+  }
+  // 64 * K * 8 + 8 * K + 20 bytes within 64 KB: K <= 125 (65 024 bytes); nothing is enqueued before this check
+  RN_CHECK_ARG(lds_ct <= 64 * 1024,
+               "rn_detect_per_class: K=%d > 125: a compaction sub-tile of 64 x K survivors does not fit 64 KB of LDS", K);
   hipStream_t st = (hipStream_t)stream;
   DetectWs w = detect_ws_layout(workspace, B, A, K, max_det);
   RN_CHECK_HIP(hipMemsetAsync(w.counts, 0, (size_t)B * K * 4, st));
@@ -1281,13 +1290,6 @@ extern "C" int rn_detect_per_class(const float* const* class_logits, const int64
   float x_skip = -INFINITY;
   if (score_threshold > 0.0f && score_threshold < 1.0f)
     x_skip = (float)(log((double)score_threshold / (1.0 - (double)score_threshold)) - 1e-3);
-  int cap_list = RN_CT_ANCHORS * K + RN_CT_ANCHORS * K / 4;   // survivors' list: one sub-tile at worst + a quarter
-  size_t lds_ct = rn_align_up((size_t)cap_list * 8 + 4 + (size_t)K * 8 + 16, 16);
-  if (lds_ct > 64 * 1024) {   // many classes: exactly one sub-tile (every sub-tile with a survivor then flushes at once)
-    cap_list = RN_CT_ANCHORS * K;
-    lds_ct = rn_align_up((size_t)cap_list * 8 + 4 + (size_t)K * 8 + 16, 16);
-  }
-  RN_CHECK_ARG(K <= 255 && lds_ct <= 64 * 1024, "rn_detect_per_class: K=%d too large for the compaction tile", K);
   hipLaunchKernelGGL(compact_logits_kernel, dim3(ct.tile_begin[num_levels]), dim3(RN_PP_THREADS), lds_ct, st, lv,
                      ct, B, K, score_threshold, x_skip, w.counts, w.keys, A, cap_list);
   RN_CHECK_LAUNCH();
