@@ -675,6 +675,24 @@ int rn_balance_features_bwd(void* const* dout, void* const* in, void* const* din
  *                      last bucket's all-reduce); if some rank's clip fired, `apply` with correction != NULL writes
  *                      (factor - 1) * g, which is all-reduced and added — the sum then equals the reference's
  *                      clip-then-all-reduce order (executor.py:432-437).
+ *   rn_optim_clip_apply_accumulate: stage 3 of a gradient-accumulation micro-step (training.gradient_accumulation_steps:
+ *                      micro-steps on one device are the reference's replicas taken one after another).  accum has the
+ *                      layout of grads, reserved slots [0:4] included.  grads holds the stage-1 tensor t and is NOT
+ *                      written; with factor = the per-tensor times the global factor of stage 2, in fp32, in the order
+ *                      written, each operation rounded once:
+ *                          first != 0:  accum[i] = factor[tensor] * t[i]              (accum is not read: whatever it
+ *                                                                                      held, NaN included, is gone)
+ *                          first == 0:  accum[i] = accum[i] + factor[tensor] * t[i]
+ *                      Access rules of rn_optim_step: 16 bytes per lane and array where the block's fp32 offset is a
+ *                      multiple of 4, a scalar tail, a scalar loop for other offsets; nothing outside tensor elements is
+ *                      written, except that one thread of the launch writes
+ *                          accum[0] = max(first ? 0 : accum[0], metrics[4] or metrics[5])
+ *                          accum[1] = max(first ? 0 : accum[1], metrics[5])
+ *                      so that accum + 1 is the skip_flag of rn_optim_step and both ride in the all-reduce of accum as
+ *                      grads[0:2] do; accum[2:4] and all padding are never written.  RN_EINVAL before any launch: a null
+ *                      pointer, accum == grads, a workspace smaller than rn_optim_workspace_bytes.
+ *   rn_optim_clip_accumulate: rn_optim_clip_prepare over all blocks, rn_optim_clip_factors (flags == NULL) and
+ *                      rn_optim_clip_apply_accumulate in one call; the same argument checks before the first launch.
  *   rn_optim_step      the update rule, the moving average and the 16-bit copy of w: the contract further down.
  */
 int rn_optim_chunk(void);
@@ -690,6 +708,13 @@ int rn_optim_clip_factors(const void* segs_dev, int num_segments, int num_blocks
                           float* metrics, float* flags, void* workspace, size_t workspace_bytes, void* stream);
 int rn_optim_clip_apply(float* grads, float* correction, const void* segs_dev, const int32_t* block_seg_dev,
                         int num_blocks, void* workspace, size_t workspace_bytes, void* stream);
+int rn_optim_clip_apply_accumulate(const float* grads, float* accum, int first, const float* metrics,
+                                   const void* segs_dev, const int32_t* block_seg_dev, int num_blocks, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int rn_optim_clip_accumulate(float* grads, const float* params, float* accum, int first, const void* segs_dev,
+                             int num_segments, const int32_t* block_seg_dev, int num_blocks, float wd_coeff,
+                             float wd_alpha, float grad_unscale, float clipnorm, float* metrics, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /*
  * The parameter update: SGD, Adam, RMSprop and Adagrad of Keras optimizer_v2 (TF 2.8) over the arenas, segment table and

@@ -227,6 +227,89 @@ extern "C" int rn_optim_clip_apply(float* grads, float* correction, const void* 
   return RN_OK;
 }
 
+// Stage 3 of a gradient-accumulation micro-step: a <- factor[tensor] * t (FIRST: a is not read), else a <- a + factor[tensor] * t.
+// t is read only.  Thread 0 of block 0 folds the micro-step's flags into a[0:2] (max over the micro-steps).
+template <bool FIRST>
+__global__ void __launch_bounds__(OPT_THREADS)
+optim_accumulate_kernel(const float* __restrict__ t, float* __restrict__ a, const float* __restrict__ metrics,
+                        const OptSeg* __restrict__ segs, const int* __restrict__ block_seg,
+                        const float* __restrict__ factor) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const float fired = (metrics[4] != 0.0f || metrics[5] != 0.0f) ? 1.0f : 0.0f, bad = metrics[5];
+    a[0] = FIRST ? fmaxf(0.0f, fired) : fmaxf(a[0], fired);
+    a[1] = FIRST ? fmaxf(0.0f, bad) : fmaxf(a[1], bad);
+  }
+  const int si = block_seg[blockIdx.x];
+  const OptSeg s = segs[si];
+  const float f = factor[si];
+  const long long b0 = (long long)(blockIdx.x - s.block_begin) * OPT_CHUNK;
+  long long b1 = b0 + OPT_CHUNK;
+  if (b1 > s.size) b1 = s.size;
+  auto one = [&](const long long o) {
+    const float p = f * t[o];
+    a[o] = FIRST ? p : a[o] + p;
+  };
+  if (((s.offset + b0) & 3) == 0) {   // 16 bytes per lane and array; scalar tail
+    const long long base = s.offset + b0;
+    const int n = (int)(b1 - b0), n4 = n >> 2;
+    const float4* t4 = (const float4*)(t + base);
+    float4* a4 = (float4*)(a + base);
+    for (int i = threadIdx.x; i < n4; i += OPT_THREADS) {
+      const float4 tv = t4[i];
+      float4 p = make_float4(f * tv.x, f * tv.y, f * tv.z, f * tv.w);
+      if constexpr (!FIRST) {
+        const float4 av = a4[i];
+        p = make_float4(av.x + p.x, av.y + p.y, av.z + p.z, av.w + p.w);
+      }
+      a4[i] = p;
+    }
+    if ((int)threadIdx.x < (n & 3)) one(base + 4 * n4 + threadIdx.x);
+  } else {
+    for (long long i = b0 + threadIdx.x; i < b1; i += OPT_THREADS) one(s.offset + i);
+  }
+}
+
+// Stage 3, accumulate form (gradient accumulation: the contract is in include/rnet_hip.h)
+extern "C" int rn_optim_clip_apply_accumulate(const float* grads, float* accum, int first, const float* metrics,
+                                              const void* segs_dev, const int32_t* block_seg_dev, int num_blocks,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+  RN_CHECK_ARG(grads && accum && metrics && segs_dev && block_seg_dev && workspace && num_blocks > 0,
+               "rn_optim_clip_apply_accumulate: bad argument");
+  RN_CHECK_ARG(accum != grads, "rn_optim_clip_apply_accumulate: accum and grads are the same arena");
+  RN_CHECK_ARG(workspace_bytes >= rn_optim_workspace_bytes(num_blocks, 1),
+               "rn_optim_clip_apply_accumulate: workspace too small");
+  const OptWs w = opt_ws(workspace, num_blocks);
+  if (first)
+    hipLaunchKernelGGL((optim_accumulate_kernel<true>), dim3(num_blocks), dim3(OPT_THREADS), 0, (hipStream_t)stream, grads,
+                       accum, metrics, (const OptSeg*)segs_dev, block_seg_dev, w.factor);
+  else
+    hipLaunchKernelGGL((optim_accumulate_kernel<false>), dim3(num_blocks), dim3(OPT_THREADS), 0, (hipStream_t)stream, grads,
+                       accum, metrics, (const OptSeg*)segs_dev, block_seg_dev, w.factor);
+  RN_CHECK_LAUNCH();
+  return RN_OK;
+}
+
+// One micro-step's clip: stages 1 and 2 on grads alone, then factor * t into (first) or onto the accumulator
+extern "C" int rn_optim_clip_accumulate(float* grads, const float* params, float* accum, int first, const void* segs_dev,
+                                        int num_segments, const int32_t* block_seg_dev, int num_blocks, float wd_coeff,
+                                        float wd_alpha, float grad_unscale, float clipnorm,
+                                        float* metrics /* dev f32[8] */, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+  RN_CHECK_ARG(grads && params && accum && segs_dev && block_seg_dev && metrics && workspace && num_segments > 0 &&
+                   num_blocks > 0, "rn_optim_clip_accumulate: bad argument");
+  RN_CHECK_ARG(accum != grads, "rn_optim_clip_accumulate: accum and grads are the same arena");
+  RN_CHECK_ARG(workspace_bytes >= rn_optim_workspace_bytes(num_blocks, num_segments),
+               "rn_optim_clip_accumulate: workspace too small");
+  int rc = rn_optim_clip_prepare(grads, params, segs_dev, block_seg_dev, num_blocks, 0, num_blocks, wd_coeff,
+                                 grad_unscale, nullptr, workspace, workspace_bytes, stream);
+  if (rc) return rc;
+  rc = rn_optim_clip_factors(segs_dev, num_segments, num_blocks, clipnorm, wd_alpha, metrics, nullptr, workspace,
+                             workspace_bytes, stream);
+  if (rc) return rc;
+  return rn_optim_clip_apply_accumulate(grads, accum, first, metrics, segs_dev, block_seg_dev, num_blocks, workspace,
+                                        workspace_bytes, stream);
+}
+
 extern "C" int rn_optim_clip(float* grads, const float* params, const void* segs_dev, int num_segments,
                              const int32_t* block_seg_dev, int num_blocks, float wd_coeff, float wd_alpha,
                              float grad_unscale, float clipnorm, float* metrics /* dev f32[8] */, void* workspace,

@@ -67,6 +67,28 @@ class Config:
         return self._params
 
 
+def gradient_accumulation_steps(params):
+    """`training.gradient_accumulation_steps`: micro-batches per optimizer step, an integer >= 1; a config without the key
+    (every reference config) means 1."""
+    n = getattr(getattr(params, "training", None), "gradient_accumulation_steps", None)
+    if n is None:
+        return 1
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"`training.gradient_accumulation_steps` must be an integer >= 1, not {n!r}")
+    return n
+
+
+def micro_batch_size(batch_size, num_replicas, accumulation_steps):
+    """Images per rank and micro-step: `training.batch_size.train` stays the images of one optimizer step, spread over
+    num_replicas ranks times accumulation_steps micro-steps."""
+    batch_size, num_replicas, accumulation_steps = int(batch_size), int(num_replicas), int(accumulation_steps)
+    parts = num_replicas * accumulation_steps
+    if parts < 1 or batch_size < parts or batch_size % parts:
+        raise ValueError(f"`training.batch_size.train` {batch_size} is not divisible by {num_replicas} replicas x "
+                         f"{accumulation_steps} gradient accumulation steps")
+    return batch_size // parts
+
+
 def default_params(input_size=640, batch_train=256, batch_val=8, activation="relu", balanced=True,
                    precision="mixed_bfloat16", inference_batch=1, nms_mode="PerClassHardNMS",
                    strategy="gpu", freeze=("resnet_initial",)):

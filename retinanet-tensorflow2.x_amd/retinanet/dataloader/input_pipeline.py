@@ -27,6 +27,7 @@ import os
 import numpy as np
 import torch
 
+from retinanet.cfg import gradient_accumulation_steps, micro_batch_size
 from retinanet.dataloader.label_encoder import LabelEncoder
 from retinanet.dataloader.preprocessing_pipeline import PreprocessingPipeline
 from retinanet.dataloader.tfrecord_parser import TFRecordDataset, parse_example
@@ -104,6 +105,7 @@ class InputPipeline:
         self.is_multi_host = is_multi_host
         self.num_replicas = num_replicas
         self.batch_size = params.training.batch_size[run_mode]
+        self.accumulation_steps = gradient_accumulation_steps(params)
         self.shuffle_buffer_size = params.dataloader_params.shuffle_buffer_size
         self.tfrecord_files = params.dataloader_params.tfrecords[run_mode]
         self._params, self._device, self._label_encoder = params, device, None   # anchors are built on first use
@@ -144,11 +146,22 @@ class InputPipeline:
     def _records(self, input_context):
         return interleave((TFRecordDataset(f) for f in self._files(input_context)), self.cycle_length, 1)
 
-    def __call__(self, input_context=None):
+    def micro_batch_size(self, input_context=None):
+        """Images of one `next()`: the per-replica share of `training.batch_size[run_mode]`, and for "train" with
+        `training.gradient_accumulation_steps` = N > 1 one N-th of it — the Executor pulls N per optimizer step."""
         batch_size = self.batch_size
-        pid = 0
+        replicas = 1
         if input_context is not None and input_context.num_replicas_in_sync > 1:
             batch_size = input_context.get_per_replica_batch_size(self.batch_size)
+            replicas = input_context.num_replicas_in_sync
+        if self.run_mode == "train" and self.accumulation_steps > 1:
+            batch_size = micro_batch_size(self.batch_size, replicas, self.accumulation_steps)
+        return batch_size
+
+    def __call__(self, input_context=None):
+        batch_size = self.micro_batch_size(input_context)
+        pid = 0
+        if input_context is not None and input_context.num_replicas_in_sync > 1:
             pid = int(input_context.input_pipeline_id)
         records = self._records(input_context)
         if self.run_mode == "val":

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from retinanet import tf_checkpoint
+from retinanet.cfg import gradient_accumulation_steps, micro_batch_size
 from retinanet.eval import COCOEvaluator
 
 
@@ -126,6 +127,7 @@ class Executor:
         self.val_freq = params.training.validation_freq
         self.steps_per_execution = params.training.steps_per_execution
         self.batch_size = params.training.batch_size
+        self.accumulation_steps = gradient_accumulation_steps(params)   # micro-batches per optimizer step (1: none)
         self.model_dir = os.path.join(params.experiment.model_dir, params.experiment.name)
         self.save_every = params.training.save_every
         self.summary_dir = params.experiment.tensorboard_dir
@@ -205,8 +207,11 @@ class Executor:
             if per_replica * self.num_replicas != self.batch_size["train"]:
                 raise ValueError(f"`training.batch_size.train` {self.batch_size['train']} is not divisible by "
                                  f"{self.num_replicas} replicas")
+            # training.gradient_accumulation_steps = N: the engine holds one micro-batch, N of them make an optimizer step
+            per_replica = self.train_micro_batch_size(self.params, self.num_replicas)
             self._engine = self._model.train_engine(per_replica, process_group=getattr(self.distribute_strategy, "group", None),
-                                                    world_size=self.num_replicas)
+                                                    world_size=self.num_replicas,
+                                                    accumulation_steps=self.accumulation_steps)
             if self.num_replicas > 1:     # SyncBN / normaliser messages through rn_comm when it validates on every rank
                 from retinanet import comm
                 comm.maybe_enable_native(self._engine)
@@ -392,14 +397,27 @@ class Executor:
             steps += 1
             yield self.distributed_eval_step(data, row_mask)
 
+    @staticmethod
+    def train_micro_batch_size(params, num_replicas):
+        """images the training engine holds: `training.batch_size.train` over the replicas and, with
+        `training.gradient_accumulation_steps`, over the micro-steps of an optimizer step"""
+        return micro_batch_size(params.training.batch_size["train"], num_replicas, gradient_accumulation_steps(params))
+
     def _train_step(self, data):
+        """one optimizer step; data: one (images, targets) batch, or with gradient accumulation the step's N micro-batches"""
+        if self.accumulation_steps > 1:
+            return self._engine.train_step_accumulated(
+                [(images.to(self._model.device), targets) for images, targets in data])
         images, targets = data
         return self._engine.train_step(images.to(self._model.device), targets)
 
     def distributed_train_step(self, iterator, num_steps):
         loss = None
         for _ in range(int(num_steps)):
-            loss = self._train_step(next(iterator))
+            if self.accumulation_steps > 1:     # every next() is one micro-batch (InputPipeline.micro_batch_size)
+                loss = self._train_step([next(iterator) for _ in range(self.accumulation_steps)])
+            else:
+                loss = self._train_step(next(iterator))
         self._engine.finish_step()      # loss scale / optimizer.iterations of the last step (read right after this call)
         keys = sorted(k for k, v in loss.items() if hasattr(v, "item") or isinstance(v, (int, float)))
         packed = torch.stack([torch.as_tensor(_f(loss[k]) if not hasattr(loss[k], "reshape") else loss[k],

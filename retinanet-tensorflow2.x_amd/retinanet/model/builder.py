@@ -185,15 +185,16 @@ class RetinaNetModel:
                                                  launch_opts=self.launch_opts)
         return self._engines[key]
 
-    def train_engine(self, batch_size, process_group=None, world_size=None):
+    def train_engine(self, batch_size, process_group=None, world_size=None, accumulation_steps=1):
         """The TrainEngine that serves `model(images, training=True)` and Executor._train_step for this batch size
-        (built once; rebuilt when the set of frozen layers changes)."""
+        (built once; rebuilt when the set of frozen layers changes).  accumulation_steps > 1: batch_size is the
+        micro-batch (training.gradient_accumulation_steps)."""
         from retinanet.model.train_engine import TrainEngine
-        key = (int(batch_size), world_size)
+        key = (int(batch_size), world_size) if accumulation_steps == 1 else (int(batch_size), world_size, accumulation_steps)
         if key not in self._train_engines:
             self._train_engines[key] = TrainEngine(self, batch_size, frozen_names=self._frozen,
                                                    process_group=process_group, world_size=world_size,
-                                                   launch_opts=self.launch_opts)
+                                                   launch_opts=self.launch_opts, accumulation_steps=accumulation_steps)
         return self._train_engines[key]
 
     def __call__(self, images, training=False):

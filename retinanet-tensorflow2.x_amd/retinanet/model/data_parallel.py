@@ -113,11 +113,13 @@ class GradientOverlap:
     calls finish()."""
 
     def __init__(self, lib, dev, *, G, P, metrics, segs_dev, block_seg_dev, n_blocks, n_segs, opt_ws, train_names, p_off,
-                 seg_blocks, ready_steps, small, pg, world, dp_active, side_stream):
+                 seg_blocks, ready_steps, small, pg, world, dp_active, side_stream, accumulation_steps=1):
         """G, P, metrics: the engine's gradient / parameter arenas and metric slots; segs_dev .. opt_ws: the optimizer's
         tables; train_names, p_off, seg_blocks: plan_buckets' inputs; ready_steps(): variable -> last backward step that
         writes its gradient, asked when the buckets are planned; small: the engine's SmallMessages; side_stream(): the
-        weight-gradient stream, or None while there is none."""
+        weight-gradient stream, or None while there is none; accumulation_steps > 1: the engine accumulates micro-steps,
+        whose clip needs each micro-step's whole gradient before anything is summed — the overlap stays off."""
+        self.accumulation_steps = accumulation_steps
         self.lib, self.dev, self.small, self.pg, self.world, self.dp_active = lib, dev, small, pg, world, dp_active
         self.G, self.P, self.metrics, self.opt_ws = G, P, metrics, opt_ws
         self.segs_dev, self.block_seg_dev, self.n_blocks, self.n_segs = segs_dev, block_seg_dev, n_blocks, n_segs
@@ -147,7 +149,7 @@ class GradientOverlap:
         """True when this backward pass launches the gradient all-reduce bucket by bucket (world > 1, or forced
         with RNET_C1_OVERLAP=1 for the single-replica equivalence test).  step_args: wdc, alpha, unscale, clip of the step."""
         mode = os.environ.get("RNET_C1_OVERLAP", "auto")
-        on = train_step_active and (mode == "1" or (mode != "0" and self.dp_active))
+        on = train_step_active and (mode == "1" or (mode != "0" and self.dp_active)) and self.accumulation_steps == 1
         self._works = []
         self._step_args = step_args
         self.on = on

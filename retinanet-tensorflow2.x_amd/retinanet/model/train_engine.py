@@ -112,9 +112,24 @@ class GradientJoins:
         return buf
 
 
+def mean_loss_dict(outs):
+    """The loss dict of an accumulated optimizer step from those of its micro-steps: the mean of every entry, except
+    l2-regularization, which is the last micro-step's (the weights do not change inside a step)."""
+    out = {}
+    for k, last in outs[-1].items():
+        if k == "l2-regularization" or not (torch.is_tensor(last) or isinstance(last, (int, float))):
+            out[k] = last
+            continue
+        total = outs[0][k]
+        for o in outs[1:]:
+            total = total + o[k]
+        out[k] = total / len(outs)
+    return out
+
+
 class TrainEngine:
     def __init__(self, model, batch_size, frozen_regexes=(), process_group=None, world_size=None, frozen_names=(),
-                 launch_opts=None, wide_pred_terms=None, force_dp=None):
+                 launch_opts=None, wide_pred_terms=None, force_dp=None, accumulation_steps=1):
         """launch_opts: `_C.LaunchOpts` (or a dict of its fields) copied into every rn_conv_problem / rn_wgrad_problem of
         THIS engine (include/rnet_hip.h rn_launch_opts) — kernel-family overrides for tests and A/B timing; the library
         has no process-wide knobs.
@@ -131,8 +146,14 @@ class TrainEngine:
         force_dp (default RNET_FORCE_DP=1): run the data-parallel machinery — SyncBN messages, the bucketed gradient
         all-reduce overlapped with the backward pass, the clip flag read — although this engine has ONE replica, over
         whatever process group it was given (a 1-rank `nccl` group: bench.py's `extra.dp_overhead`, the cost of that
-        machinery on one GPU; losses and gradients equal the plain step's)."""
+        machinery on one GPU; losses and gradients equal the plain step's).
+        accumulation_steps (training.gradient_accumulation_steps): N micro-batches of `batch_size` images per optimizer step,
+        taken one after another the way the reference takes its replicas side by side (DESIGN "Gradient accumulation");
+        1 = the plain train_step, and nothing of the accumulation exists."""
         self.model = model
+        self.accumulation_steps = int(accumulation_steps)
+        if self.accumulation_steps < 1:
+            raise ValueError(f"accumulation_steps must be an integer >= 1, not {accumulation_steps!r}")
         self.g = model.graph
         self.params_cfg = model.params
         self.B = int(batch_size)
@@ -224,6 +245,9 @@ class TrainEngine:
         self._ls_host = self._ls_event = None   # pinned copy of the "gradients not finite" flag and its event
         self._ls_pending = False  # that copy has not been looked at yet (_resolve_loss_scale)
         self._train_step_active = False
+        self._micro_next = 0      # the micro-step accumulate_micro_step expects next (accumulation_steps > 1)
+        self._micro_scale = 1.0   # the loss scale of the optimizer step under way: one for all its micro-steps
+        self._micro_messages = 0  # SyncBN messages of the micro-steps so far
         self._images_ref = None   # the caller's batch while forward() reads it in place
         self._step_args = dict(wdc=0.0, alpha=0.0, unscale=1.0, clip=0.0)
         self._side_stream = None
@@ -263,7 +287,7 @@ class TrainEngine:
                 block_seg_dev=self.block_seg_dev, n_blocks=self.n_blocks, n_segs=self.n_segs, opt_ws=self.opt_ws,
                 train_names=self.train_names, p_off=self.p_off, seg_blocks=self._seg_blocks, ready_steps=self._ready_steps,
                 small=self.small, pg=self.pg, world=self.world, dp_active=self.dp_active,
-                side_stream=lambda: self._side_stream)
+                side_stream=lambda: self._side_stream, accumulation_steps=self.accumulation_steps)
             for name, cp in self.conv_launches:   # a launch writes stage-1 BatchNorm partials for all its segments or none
                 marks = {bool(cp.seg[i].bn_bwd_y) for i in range(cp.num_segments)}
                 if name.startswith("dgrad:") and len(marks) != 1:
@@ -444,6 +468,8 @@ class TrainEngine:
         self.n_params = off
         self.P = torch.zeros((off,), dtype=torch.float32, device=self.dev)
         self.G = torch.zeros_like(self.P)
+        # gradient accumulation: sum over the micro-steps of factor * t, layout of G (A[0:2]: the flags; rn_optim_clip_accumulate)
+        self.A = torch.zeros_like(self.P) if self.accumulation_steps > 1 else None
         # optimizer slots: V is the step kernel's slot 0 (SGD `momentum`, Adam `m`, RMSprop `rms`, Adagrad `accumulator`);
         # S1 / S2 exist only while the configured rule has a second / third slot (_bind_optimizer)
         self.V = torch.zeros_like(self.P)
@@ -589,7 +615,11 @@ class TrainEngine:
         TensorFlow's checkpoint FILE format (where executor.py:652-654 / 695-697 call `model.save_weights`).  Interop
         is one-way: this build reads what the reference wrote (by variable name through the object graph); the
         reference's Keras `load_weights` matches structurally and will not consume the flat object graph written
-        here (retinanet/tf_checkpoint.py::save_weights)."""
+        here (retinanet/tf_checkpoint.py::save_weights).  Written between optimizer steps: the accumulator of a
+        step under way (accumulation_steps > 1) is no part of it."""
+        if self._micro_next != 0:
+            raise RuntimeError(f"save_checkpoint inside an optimizer step: {self._micro_next} of "
+                               f"{self.accumulation_steps} micro-steps accumulated")
         with torch.cuda.device(self.dev):
             self.store_to_model(use_ema=False)
             torch.cuda.synchronize()
@@ -2064,9 +2094,10 @@ class TrainEngine:
         if self.loss_scale:
             self._update_loss_scale()
 
-    def _update_loss_scale(self):
+    def _update_loss_scale(self, flags=None):
         """tf.keras.mixed_precision.LossScaleOptimizer(dynamic=True) (optimizers/builder.py:56-64): halve the scale
         when a step's gradients were not finite (the step was dropped), double it after `growth_steps` good steps.
+        flags: the arena whose slot [1] holds "not finite" (default G; the accumulated step hands in A).
 
         The step kernel drops the update itself (skip pointer); what the HOST needs — the next loss scale, whether
         optimizer.iterations advances — it needs only when the NEXT step reaches its loss: the flag goes to pinned
@@ -2077,7 +2108,7 @@ class TrainEngine:
         if self._ls_host is None:
             self._ls_host = torch.zeros((1,), dtype=torch.float32, pin_memory=True)
             self._ls_event = torch.cuda.Event()
-        self._ls_host.copy_(self.G[1:2], non_blocking=True)
+        self._ls_host.copy_((self.G if flags is None else flags)[1:2], non_blocking=True)
         self._ls_event.record(torch.cuda.current_stream(self.dev))
         self._ls_pending = True
 
@@ -2106,6 +2137,9 @@ class TrainEngine:
     def train_step(self, images, targets):
         """(images f32[B,H,W,3], targets from LabelEncoder.encode_batch) -> the loss dict of Executor._train_step
         (executor.py:409-441; device scalars)."""
+        if self.accumulation_steps != 1:
+            raise RuntimeError(f"train_step is one optimizer step over one batch; this engine accumulates "
+                               f"{self.accumulation_steps} micro-batches per step: call train_step_accumulated")
         cfg = self.params_cfg.training
         opt = self.model.optimizer
         if self.model.loss._num_replicas() != self.world:
@@ -2154,3 +2188,97 @@ class TrainEngine:
         out["gradient-norm"] = self.metrics[0] * self.world      # executor.py:440
         out["num-anchors-matched"] = loss["num-anchors-matched"] / self.B   # executor.py:439
         return out
+
+    # ---- gradient accumulation (training.gradient_accumulation_steps = N > 1; DESIGN "Gradient accumulation") -------------
+    def accumulate_micro_step(self, images, targets, index):
+        """Micro-step `index` of N: forward, loss and backward as in train_step on a micro-batch of B images, with the
+        reference's per-replica arithmetic for R * N replicas (executor.py:401-437: loss / (R N), alpha / (R N) of the decay
+        gradient, the clip on THIS micro-step's gradient alone), then factor * t into (index 0) or onto the accumulator A.
+        G holds the stage-1 tensor t afterwards.  Returns the micro-step's loss dict (values of its own, not views)."""
+        N = self.accumulation_steps
+        if N < 2:
+            raise RuntimeError("accumulate_micro_step: the engine was built with accumulation_steps = 1: call train_step")
+        if index != self._micro_next or not 0 <= index < N:
+            raise RuntimeError(f"accumulate_micro_step: micro-step {index} of {N}, expected {self._micro_next}")
+        cfg = self.params_cfg.training
+        opt = self.model.optimizer
+        if self.model.loss._num_replicas() != self.world:
+            raise RuntimeError(f"RetinaNetLoss sees {self.model.loss._num_replicas()} replicas, the engine {self.world}")
+        if opt.dynamic_loss_scale and self.loss_scale is None:
+            self.loss_scale = dict(scale=float(opt.initial_loss_scale), good=0, growth_steps=int(opt.loss_scale_growth_steps),
+                                   skipped=False)
+        replicas = self.world * N
+        with torch.cuda.device(self.dev):
+            self._bind_optimizer()
+            alpha = cfg.weight_decay_alpha if cfg.use_weight_decay else 0.0
+            self._prepack_dgrad_weights()
+            self.small.begin_step(targets["num-positives"],
+                                  carry_normalizer=not self.model.loss.use_moving_average_normalizer)
+            preds = self.forward(images)
+            if index == 0:                  # one loss scale for the N micro-steps of an optimizer step
+                self._resolve_loss_scale()
+                self._micro_scale = self.loss_scale["scale"] if self.loss_scale else 1.0
+                self._micro_messages = 0
+            scale = self._micro_scale
+            clip = float(opt.clipnorm) if opt.clipnorm else 0.0
+            self._step_args = dict(wdc=alpha / replicas, alpha=alpha, unscale=1.0 / scale, clip=clip)
+            loss = self.model.loss(targets, preds, compute_grads=True, grad_scale=scale / replicas,
+                                   grads_bf16=self.loss_grad_buffers(), normalizer=self.small.c2_normalizer)
+            self.backward(None)             # (_train_step_active stays False: no bucket leaves during a micro-step)
+            _C.check(self.lib.rn_optim_clip_accumulate(
+                self.G.data_ptr(), self.P.data_ptr(), self.A.data_ptr(), 1 if index == 0 else 0, self.segs_dev.data_ptr(),
+                self.n_segs, self.block_seg_dev.data_ptr(), self.n_blocks, alpha / replicas, alpha, 1.0 / scale, clip,
+                self.metrics.data_ptr(), self.opt_ws.data_ptr(), self.opt_ws.numel(), _C.current_stream()),
+                "rn_optim_clip_accumulate")
+            self._micro_messages += self.small.end_step()
+            self._micro_next = index + 1
+            out = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in loss.items()}
+            out["total-loss"] = out["weighted-loss"]                 # executor.py:414-419
+            if cfg.use_weight_decay:
+                out["l2-regularization"] = self.metrics[3].clone()
+                out["total-loss"] = out["weighted-loss"] + out["l2-regularization"]
+            out["gradient-norm"] = self.metrics[0] * replicas    # executor.py:440 with R * N replicas
+            out["num-anchors-matched"] = loss["num-anchors-matched"] / self.B
+        return out
+
+    def apply_accumulated(self):
+        """After micro-step N - 1: all-reduce SUM of A over the ranks (plain order), ONE rn_optim_step from A — dropped
+        under a LossScaleOptimizer when any micro-step on any rank was not finite (A[1]) —, refresh_packs, the loss-scale
+        bookkeeping and the counters of one optimizer step."""
+        N = self.accumulation_steps
+        if N < 2 or self._micro_next != N:
+            raise RuntimeError(f"apply_accumulated: {self._micro_next} of {N} micro-steps accumulated")
+        opt = self.model.optimizer
+        step = self.step_count              # read after micro-step 0 resolved the previous step's flag
+        with torch.cuda.device(self.dev):
+            if opt.name != self._slot_owner:
+                raise RuntimeError(f"apply_accumulated: the slot arenas belong to {self._slot_owner}, not {opt.name}")
+            ema_decay = opt.ema_decay(step) if opt.use_moving_average else None
+            rule = self._optim_rule(opt, opt.step_size(step), ema_decay)
+            if self.dp_active:
+                from retinanet.distribute import all_reduce_sum_bucketed
+                all_reduce_sum_bucketed(self.A, 2 if self.world == 1 else self.world, self.pg)   # executor.py:436-437
+            skip = self.A.data_ptr() + 4 if self.loss_scale else None
+            _C.check(self.lib.rn_optim_step(self.P.data_ptr(), self.A.data_ptr(), self.V.data_ptr(), _C.ptr(self.S1),
+                                            _C.ptr(self.S2), self.E.data_ptr() if ema_decay is not None else None,
+                                            self.Pbf.data_ptr(), self.segs_dev.data_ptr(), self.block_seg_dev.data_ptr(),
+                                            self.n_blocks, ctypes.byref(rule), skip, _C.current_stream()), "rn_optim_step")
+            self.refresh_packs()
+            if self.loss_scale:
+                self._update_loss_scale(self.A)
+            self.syncbn_messages_per_step = self._micro_messages
+            self._micro_next = 0
+            self.step_count += 1              # (taken back by _resolve_loss_scale when the step turns out dropped)
+            opt.iterations = self.step_count
+
+    def train_step_accumulated(self, micro_batches):
+        """One optimizer step over N (images, targets) micro-batches -> the loss dict of train_step: every loss entry and
+        num-anchors-matched the mean over the micro-steps, gradient-norm the mean of the micro-steps' clipped norms times
+        R * N, l2-regularization that of the last micro-step (the weights do not change inside a step)."""
+        micro_batches = list(micro_batches)
+        N = self.accumulation_steps
+        if len(micro_batches) != N:
+            raise ValueError(f"train_step_accumulated: {len(micro_batches)} micro-batches for accumulation_steps = {N}")
+        outs = [self.accumulate_micro_step(images, targets, i) for i, (images, targets) in enumerate(micro_batches)]
+        self.apply_accumulated()
+        return mean_loss_dict(outs)

@@ -1,7 +1,8 @@
 """Micro-benchmark of the optimizer step kernels on the training engine's own arenas (ResNet50-640: the engine's real
 segment and block tables): every mode of rn_optim_step, alternated in one process — time per launch,
-algorithmic bytes (arrays read + written) and bytes/s.
-python tools/bench_optim.py [--size 640] [--window 0.25] [--rounds 3] [--lib bf16|f16] [--no-ema]"""
+algorithmic bytes (arrays read + written) and bytes/s.  `accumulate`: the accumulate stage of gradient accumulation
+(rn_optim_clip_apply_accumulate: 12 bytes per element, 8 with `first`) alternated with the SGD rule of rn_optim_step.
+python tools/bench_optim.py [rules|accumulate] [--size 640] [--window 0.25] [--rounds 3] [--lib bf16|f16] [--no-ema]"""
 import argparse, ctypes, math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "retinanet-tensorflow2.x_amd"))
@@ -20,6 +21,7 @@ MODES = {"sgd": (_C.RN_OPT_SGD, 0, 3, 2), "sgd+nesterov": (_C.RN_OPT_SGD, _C.RN_
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("what", nargs="?", default="rules", choices=["rules", "accumulate"])
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of back-to-back launches per measurement")
     ap.add_argument("--rounds", type=int, default=3, help="measurements per mode, the modes alternated")
@@ -49,7 +51,22 @@ def main():
         return lambda: lib.rn_optim_step(eng.P.data_ptr(), eng.G.data_ptr(), eng.V.data_ptr(), S1.data_ptr(), S2.data_ptr(),
                                          E, *args, ctypes.byref(r), None, st)
 
-    calls = {name: (rule_call(rule, flags), rd, wr) for name, (rule, flags, rd, wr) in MODES.items()}
+    # name -> (launch, fp32 arrays read, written, "a rule of rn_optim_step": the moving average and the 16-bit copy come on top)
+    calls = {name: (rule_call(rule, flags), rd, wr, True) for name, (rule, flags, rd, wr) in MODES.items()}
+    if a.what == "accumulate":
+        acc = torch.zeros_like(eng.G)
+        ws = (eng.opt_ws.data_ptr(), eng.opt_ws.numel())
+        # stages 1 and 2 once: the factors the timed stage reads (a clip that fires: the stage has no branch on them)
+        _C.check(lib.rn_optim_clip_accumulate(eng.G.data_ptr(), eng.P.data_ptr(), acc.data_ptr(), 1, eng.segs_dev.data_ptr(),
+                                              eng.n_segs, eng.block_seg_dev.data_ptr(), eng.n_blocks, 0.0, 0.0, 1.0, 1e-3,
+                                              eng.metrics.data_ptr(), *ws, st), "rn_optim_clip_accumulate")
+
+        def accumulate_call(first):
+            return lambda: lib.rn_optim_clip_apply_accumulate(eng.G.data_ptr(), acc.data_ptr(), first, eng.metrics.data_ptr(),
+                                                              eng.segs_dev.data_ptr(), eng.block_seg_dev.data_ptr(),
+                                                              eng.n_blocks, *ws, st)
+        calls = {"sgd": calls["sgd"], "accumulate": (accumulate_call(0), 2, 1, False),
+                 "accumulate first": (accumulate_call(1), 1, 1, False)}
 
     def timed(fn, name, reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -61,14 +78,14 @@ def main():
         return e0.elapsed_time(e1) / reps * 1e-3          # seconds per launch
 
     reps = {}
-    for name, (fn, _, _) in calls.items():                # warm, and size the window
+    for name, (fn, _, _, _) in calls.items():             # warm, and size the window
         timed(fn, name, 5)
         reps[name] = max(10, math.ceil(a.window / timed(fn, name, 20)))
         eng.V.fill_(0.1)                                  # a state every rule can continue from
         S1.zero_(), S2.fill_(0.1)
     times = {name: [] for name in calls}
     for _ in range(a.rounds):
-        for name, (fn, _, _) in calls.items():
+        for name, (fn, _, _, _) in calls.items():
             times[name].append(timed(fn, name, reps[name]))
             eng.V.fill_(0.1)
             S1.zero_(), S2.fill_(0.1)
@@ -76,9 +93,10 @@ def main():
           f"moving average {'on' if ema else 'off'}, build {a.lib}", flush=True)
     print(f"{'mode':28s} {'arrays r+w':>10s} {'MB':>8s} {'us (median)':>12s} {'us (min)':>9s} {'GB/s':>7s} {'vs sgd':>7s}")
     base = None
-    for name, (fn, rd, wr) in calls.items():
-        rd, wr = rd + (1 if ema else 0), wr + (1 if ema else 0)
-        nbytes = 4 * n * (rd + wr) + 2 * n16
+    for name, (fn, rd, wr, rule) in calls.items():
+        if rule:
+            rd, wr = rd + (1 if ema else 0), wr + (1 if ema else 0)
+        nbytes = 4 * n * (rd + wr) + (2 * n16 if rule else 0)
         t = sorted(times[name])
         med = t[len(t) // 2]
         gbs = nbytes / med / 1e9
