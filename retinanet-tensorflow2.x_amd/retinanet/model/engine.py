@@ -93,23 +93,12 @@ class InferenceEngine:
     # ---- weights -----------------------------------------------------------------------------
     def load_variables(self, variables):
         """(Re)pack conv kernels and refold BN/bias from a name -> tensor dict (in place after the first call)."""
-        lib, st, fc = self.lib, _C.current_stream(), self.folded
+        fc = self.folded
         for op in self.g.ops:
             if op["op"] == "se":
-                name = op["se"]
-                se = self.g.ses[name]
-                f32 = lambda n: variables[name + n].to(self.dev, torch.float32)
-                fc.stable(name + ":w1", f32("/conv2d/kernel").reshape(se["C"], se["se"]).t().to(self.h16))
-                fc.stable(name + ":b1", f32("/conv2d/bias"))
-                fc.stable(name + ":w2", f32("/conv2d_1/kernel").reshape(se["se"], se["C"]).t().to(self.h16))
-                fc.stable(name + ":b2", f32("/conv2d_1/bias"))
+                fc.load_se(variables, op)
             elif op["op"] == "dwconv":
-                d = self.g.dws[op["dw"]]
-                w = variables[d["kvar"]].to(self.dev, torch.float32).contiguous()
-                buf = fc.buffer(op["dw"], (d["k"] * d["k"], d["C"]))
-                _C.check(lib.rn_pack_depthwise_weight(_C.ptr(w), d["k"], d["C"], _C.ptr(buf), st),
-                         "rn_pack_depthwise_weight")
-                fc.refold(op["out"], fold_bn(variables, op.get("bn"), None, self.eps, self.dev))
+                fc.load_dw(variables, op)
             elif op["op"] in ("conv", "stem") and op["out"] not in self._bneck_skip:   # fused blocks: packed below
                 fc.load(variables, op)
             elif op["op"] == "topdown" and op.get("fusion"):
@@ -170,9 +159,7 @@ class InferenceEngine:
         p = dw_problem(self.g, ops, self.B, lambda o: self.t[o["inp"]], lambda o: self.t[o["out"]],
                        lambda o: self.folded.packed[o["dw"]].data_ptr(), _C.ACT_IDS[ops[0]["act"]])
         for i, op in enumerate(ops):
-            scale, shift, _ = self.folded.fold[op["out"]]
-            p.seg[i].scale = scale.data_ptr() if scale is not None else None
-            p.seg[i].shift = shift.data_ptr() if shift is not None else None
+            self.folded.fill_dw(p.seg[i], op)
         self._keep.append(p)
         lib = self.lib
         pref = ctypes.byref(p)
@@ -241,10 +228,7 @@ class InferenceEngine:
             elif kind == "se":
                 x = self.t[op["tensor"]]
                 name, se = op["se"], self.g.ses[op["se"]]
-                pk = self.folded.packed
-                args = (x.data_ptr(), B, x.shape[1] * x.shape[2], se["C"], pk[name + ":w1"].data_ptr(),
-                        pk[name + ":b1"].data_ptr(), pk[name + ":w2"].data_ptr(), pk[name + ":b2"].data_ptr(), se["se"],
-                        self.se_ws.data_ptr(), self.se_ws.numel())
+                args = self.folded.se_args(op, x, B, self.se_ws)
                 self.se_launches.append(("se:" + op["tensor"], B, x.shape[1] * x.shape[2], se["C"], se["se"]))
 
                 def se_run(st, args=args, name=name):

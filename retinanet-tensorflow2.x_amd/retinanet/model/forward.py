@@ -245,6 +245,39 @@ class FoldedConvs:
             fold = fold[:2] + (torch.nn.functional.pad(fold[2], (0, -fold[2].numel() % 4)),)
         self.refold(op["out"], fold)
 
+    def load_dw(self, variables, op):
+        """(re)pack the [k][k][C][1] kernel of depthwise op `op` to [k*k][C] and refold its BatchNorm"""
+        d = self.g.dws[op["dw"]]
+        w = variables[d["kvar"]].to(self.dev, torch.float32).contiguous()
+        buf = self.buffer(op["dw"], (d["k"] * d["k"], d["C"]))
+        _C.check(self.lib.rn_pack_depthwise_weight(_C.ptr(w), d["k"], d["C"], _C.ptr(buf), _C.current_stream()),
+                 "rn_pack_depthwise_weight")
+        self.refold(op["out"], fold_bn(variables, op.get("bn"), None, self.eps, self.dev))
+
+    def load_se(self, variables, op):
+        """the two 1x1 kernels ([out][in], storage type) and f32 biases of squeeze-excite op `op`, as
+        rn_squeeze_excite_inplace reads them: `<se>:w1`, `:b1`, `:w2`, `:b2`"""
+        name = op["se"]
+        se = self.g.ses[name]
+        f32 = lambda n: variables[name + n].to(self.dev, torch.float32)
+        self.stable(name + ":w1", f32("/conv2d/kernel").reshape(se["C"], se["se"]).t().to(self.h16))
+        self.stable(name + ":b1", f32("/conv2d/bias"))
+        self.stable(name + ":w2", f32("/conv2d_1/kernel").reshape(se["se"], se["C"]).t().to(self.h16))
+        self.stable(name + ":b2", f32("/conv2d_1/bias"))
+
+    def se_args(self, op, x, B, ws):
+        """arguments of rn_squeeze_excite_inplace for op `op` on tensor x (workspace ws), without the stream"""
+        name, se, pk = op["se"], self.g.ses[op["se"]], self.packed
+        return (x.data_ptr(), B, x.shape[1] * x.shape[2], se["C"], pk[name + ":w1"].data_ptr(), pk[name + ":b1"].data_ptr(),
+                pk[name + ":w2"].data_ptr(), pk[name + ":b2"].data_ptr(), se["se"], ws.data_ptr(), ws.numel())
+
+    def fill_dw(self, seg, op):
+        """weights and inference-form epilogue (folded BatchNorm) of the segment of depthwise op `op`"""
+        scale, shift, _ = self.fold[op["out"]]
+        seg.w = self.packed[op["dw"]].data_ptr()
+        seg.scale = scale.data_ptr() if scale is not None else None
+        seg.shift = shift.data_ptr() if shift is not None else None
+
     def fill(self, seg, op, t):
         """weights and inference-form epilogue of the segment of conv `op`: folded scale / shift / bias, residual"""
         scale, shift, bias = self.fold[op["out"]]

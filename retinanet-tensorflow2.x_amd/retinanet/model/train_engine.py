@@ -14,7 +14,9 @@ scheduled from the same static graph as the forward pass.
     per-group [sum, sumsq] / [sum g, sum g*xhat] vectors are all-reduced between the stages
     (SyncBatchNormalization, model/utils.py:10-12);
   * layers frozen whole (training.freeze_variables, executor.py:154-176) keep inference-mode BN folded
-    into their conv epilogue and get no backward at all; a frozen BatchNorm under a trainable conv
+    into their conv / depthwise epilogue and get no backward at all while nothing below them trains; above trainable
+    layers (`fpn`, `head`) they run like the next form without weight, bias, gamma or beta gradients, their
+    data-gradient weight packs made once when weights are loaded; a frozen BatchNorm under a trainable conv
     (the `bn` / `*-bn` keys) runs in inference mode inside the step: the raw conv launch, rn_bn_apply
     with a constant scale / shift table, and one elementwise rn_bn_frozen_bwd in the backward pass —
     no statistics, no reductions, no gamma / beta gradients, no SyncBN message (DESIGN.md section 7b);
@@ -214,6 +216,7 @@ class TrainEngine:
         for k in model.variables:
             if any(rx.search(k) for rx in frozen_regexes):
                 self.frozen.add(k)
+        self._check_frozen_layers()
         # ---- what the build records
         self._keep = []
         self._algo = {}           # id(rn_conv_problem) -> (algorithmic FLOPs, algorithmic bytes) where the launch executes more
@@ -233,6 +236,9 @@ class TrainEngine:
         self.dy_of = {}           # conv output -> gradient at the conv's own (pre-BatchNorm) output, what wgrad / dgrad read
         self._loss_dy = None      # loss_grad_buffers(): the prediction convs' entries of dy_of
         self._dgrad_pack_items = None   # rn_dgrad_pack array over dgrad_packs
+        self.frozen_dgrad_packs = []    # (kernel variable, conv dims, packed buffer, mode) of frozen convs: packed on load
+        self.frozen_dw_flip_packs = []  # (kernel variable, k, C, packed buffer) of frozen depthwise layers: packed on load
+        self._frozen_folded = False     # _fold_frozen has run: load_from_model re-enters it
         self.drop_connect = True     # stochastic depth of the EfficientNet skip blocks (efficientnet.py:97-113)
         self.fusion_state = {}       # id(weighted top-down op) -> forward.FusionState (weights, coefficient blocks)
         self.dc_masks = {}           # project conv output -> (f32[B] factors, survival_prob)
@@ -295,9 +301,10 @@ class TrainEngine:
 
     # ------------------------------------------------------------------------------------------
     def _prepare_graph(self):
-        """Engine-local copy of the op list: squeeze-excite runs out of place in training (its backward
-        needs the un-gated input), so `se` ops get an output tensor `<t>:se` and later readers of `<t>` are
-        redirected to it.  Also classifies every variable (compute layout, weight decay)."""
+        """Engine-local copy of the op list: a trainable squeeze-excite runs out of place in training (its backward
+        needs the un-gated input), so such `se` ops get an output tensor `<t>:se` and later readers of `<t>` are
+        redirected to it; a frozen one gates `<t>` in place as the serving engine does (inp = out = `<t>`).  Also
+        classifies every variable (compute layout, weight decay)."""
         g = self.g
         self.tensors = dict(g.tensors)
         self.ops = []
@@ -307,7 +314,9 @@ class TrainEngine:
             for key in ("inp", "residual"):
                 if o.get(key) in alias:
                     o[key] = alias[o[key]]
-            if o["op"] == "se":
+            if o["op"] == "se" and not self._se_trainable(o):
+                o["inp"] = o["out"] = alias.get(o["tensor"], o["tensor"])
+            elif o["op"] == "se":
                 t = o["tensor"]
                 o["inp"], o["out"] = alias.get(t, t), t + ":se"
                 self.tensors[o["out"]] = g.tensors[t]
@@ -350,17 +359,65 @@ class TrainEngine:
         """BatchNorm in inference mode under a trainable conv (the `bn` / `*-bn` freeze patterns)"""
         return bool(op.get("bn")) and self._conv_trainable(op) and not self._bn_trainable(op)
 
+    _SE_VARS = ("/conv2d/kernel", "/conv2d/bias", "/conv2d_1/kernel", "/conv2d_1/bias")
+
+    def _se_trainable(self, op):
+        return (op["se"] + self._SE_VARS[0]) not in self.frozen
+
+    def _launch_of(self, op):
+        """the ops of the launch conv / depthwise `op` runs in: its group, or the op alone"""
+        return [op] if op.get("group") is None else self._group_ops(op["op"], op["group"])
+
+    def _passes_gradient(self, op):
+        """the launch of frozen conv / depthwise `op` hands a gradient down: an input or residual of one of its ops needs one"""
+        return any(self.requires.get(i) for o in self._launch_of(op) for i in (o["inp"], o.get("residual")) if i)
+
+    def _bn_apart(self, op):
+        """BatchNorm in inference mode as a step of its own — the raw conv output, then rn_bn_apply on the constant scale /
+        shift table: under a trainable conv (_bn_frozen); under a frozen conv whose launch hands a gradient down (the gate
+        bits and rn_bn_frozen_bwd need the step); under the frozen project conv of a drop_connect block, whose per-image
+        factor stands between the BatchNorm and the residual add where the folded conv epilogue has no place for it."""
+        if not op.get("bn") or self._bn_trainable(op):
+            return False
+        if self._conv_trainable(op):
+            return True
+        return self._passes_gradient(op) or (self.drop_connect and any(o.get("survival") is not None
+                                                                      for o in self._launch_of(op)))
+
     def _inference_form(self, op):
         return not self._conv_trainable(op) and not self._bn_trainable(op) and not self.requires.get(op["inp"])
+
+    def _check_frozen_layers(self):
+        """The reference freezes per Keras layer (executor.py:168-175), this engine per variable name: the two agree when
+        every layer's variables are frozen together, which the eight FREEZE_VARS_REGEX patterns guarantee."""
+        g = self.g
+        layers = [[b + sfx for sfx in ("/gamma", "/beta", "/moving_mean", "/moving_variance")] for b in g.bns]
+        layers += [[s + sfx for sfx in self._SE_VARS] for s in getattr(g, "ses", {})]
+        dws = getattr(g, "dws", {})
+        for cname, c in g.convs.items():
+            names = [c.get("kvar", cname + "/kernel")] + ([cname + "/bias"] if c["bias"] else [])
+            if cname + ":dw" in dws:      # SeparableConv2D: depthwise_kernel, pointwise_kernel and bias are one layer
+                names.append(dws[cname + ":dw"]["kvar"])
+            layers.append(names)
+        for names in layers:
+            n = sum(k in self.frozen for k in names)
+            if 0 < n < len(names):
+                raise ValueError(f"freeze patterns split a layer: {[k for k in names if k in self.frozen]} frozen, "
+                                 f"{[k for k in names if k not in self.frozen]} not (the reference freezes whole layers)")
 
     def _analyse(self):
         self.requires = {"images": False}
         for op in self.ops:
             kind = op["op"]
-            if kind in ("conv", "stem"):
-                tr = self._conv_trainable(op) or bool(self._bn_trainable(op))
-                ins = [op["inp"]] + ([op["residual"]] if op.get("residual") else [])
-                self.requires[op["out"]] = tr or any(self.requires[i] for i in ins)
+            if kind in ("conv", "stem", "dwconv"):
+                # a grouped launch stands where its first op does and has one form: a frozen one hands a gradient down
+                # when any of its ops' inputs needs one
+                if op["out"] in self.requires:
+                    continue
+                launch = self._launch_of(op)
+                below = any(self.requires[i] for o in launch for i in (o["inp"], o.get("residual")) if i)
+                for o in launch:
+                    self.requires[o["out"]] = self._conv_trainable(o) or bool(self._bn_trainable(o)) or below
             elif kind == "maxpool":
                 self.requires[op["out"]] = self.requires[op["inp"]]
             elif kind == "topdown":
@@ -374,14 +431,14 @@ class TrainEngine:
                     self.requires[o] = r or self.requires.get(o, False)
             elif kind == "balance":
                 pass
-            elif kind == "dwconv":
-                if not self._conv_trainable(op):
-                    raise NotImplementedError("frozen depthwise layers are not a shipped configuration")
-                self.requires[op["out"]] = True
             elif kind == "se":
-                if any((op["se"] + sfx) in self.frozen for sfx in ("/conv2d/kernel", "/conv2d_1/kernel")):
-                    raise NotImplementedError("frozen squeeze-excite layers are not a shipped configuration")
-                self.requires[op["out"]] = True
+                if not self._se_trainable(op) and self.requires[op["inp"]]:
+                    # squeeze-excite sits in the backbone, the bottom of the model: no freeze pattern leaves a frozen one
+                    # above a trainable layer, and there is no backward of it without its weight gradients
+                    raise NotImplementedError(f"squeeze-excite {op['se']} is frozen while layers below it train: its "
+                                              "backward without weight gradients is not built (no freeze pattern "
+                                              "produces it)")
+                self.requires[op["out"]] = self._se_trainable(op)
             else:
                 raise NotImplementedError(f"training through '{kind}' ops is not built")
         # The reference's `backbone` / `resnet_initial` freeze patterns exclude fpn, box-head and class-head by name, not
@@ -517,7 +574,10 @@ class TrainEngine:
         for (off, n), bfo in self._bf_copies:
             self.Pbf[bfo:bfo + n].copy_(self.P[off:off + n])
         self.refresh_packs()
-        self._fill_frozen_bn()
+        if self._frozen_folded:     # a reload: the frozen layers' packed weights, folded BatchNorm and data-gradient packs
+            self._fold_frozen()
+        else:
+            self._fill_frozen_bn()
 
     def _bind_optimizer(self, reset=False):
         """Slot arenas for the optimizer the model holds NOW (tests and tools replace `model.optimizer` after the engine
@@ -707,15 +767,16 @@ class TrainEngine:
         self.stem_k, self.stem_pad, self.Hp, self.Wp, self.stem_in = stem_input(self.tensors, self._stem_op(), B, self.h16,
                                                                                 dev)
         for op in self.ops:
-            if op["op"] in ("conv", "stem", "dwconv") and (self._bn_trainable(op) or self._bn_frozen(op)):
+            if op["op"] in ("conv", "stem", "dwconv") and (self._bn_trainable(op) or self._bn_apart(op)):
                 self.raw[op["out"]] = torch.empty_like(self.t[op["out"]])
-        # squeeze-excite: saved forward state per op + one shared workspace
+        # squeeze-excite: saved forward state per trainable op + one shared workspace (a frozen one keeps no state)
         self.se_state = {}
         se_bytes = 0
         for op in self.ops:
             if op["op"] == "se":
                 nb = self.lib.rn_se_workspace_bytes(B, self.g.ses[op["se"]]["C"])
-                self.se_state[op["out"]] = torch.empty((nb,), dtype=torch.uint8, device=dev)
+                if self._se_trainable(op):
+                    self.se_state[op["out"]] = torch.empty((nb,), dtype=torch.uint8, device=dev)
                 se_bytes = max(se_bytes, nb)
         self.se_ws = torch.empty((max(se_bytes, 16),), dtype=torch.uint8, device=dev)
         # balance features runs out of place in training (its backward needs the inputs)
@@ -744,7 +805,8 @@ class TrainEngine:
             H, W, C, _ = self.tensors[n]
             self.grad[n] = torch.zeros((B, H, W, C), dtype=self.h16, device=dev)
         for n, t in self.bal_out.items():
-            self.grad["bal:" + n] = torch.zeros_like(t)
+            if self.requires.get(n):
+                self.grad["bal:" + n] = torch.zeros_like(t)
         self.bn_state = {}
         for op in self.ops:
             if op["op"] in ("conv", "stem", "dwconv") and self._bn_trainable(op):
@@ -753,16 +815,40 @@ class TrainEngine:
                                      "mv": self.model.variables[bn + "/moving_variance"].to(dev, torch.float32).clone()}
 
     def _fold_frozen(self):
-        """inference-mode scale/shift + packed weights for frozen conv(+BN) layers (in place after the first call)."""
+        """inference-mode scale/shift + packed weights for frozen conv / depthwise (+BN) and squeeze-excite layers, and
+        the data-gradient weight packs of those that hand a gradient down (in place after the first call)."""
         for op in self.ops:
             if op["op"] in ("conv", "stem") and not self._conv_trainable(op) and op["out"] not in self._bneck_skip:
                 self.folded.load(self.model.variables, op)
+            elif op["op"] == "dwconv" and not self._conv_trainable(op):
+                self.folded.load_dw(self.model.variables, op)
+            elif op["op"] == "se" and not self._se_trainable(op):
+                self.folded.load_se(self.model.variables, op)
             elif op["op"] == "topdown" and op.get("fusion"):   # frozen fusion weights: f32 copies at stable addresses
                 for name in (n for pair in op["fusion_vars"] for n in pair if n in self.frozen):
                     self.folded.stable(name, self.model.variables[name].to(self.dev, torch.float32).reshape(-1).clone())
         for fb in self.bneck.values():
             fb.load(self.model.variables, self.eps)
         self._fill_frozen_bn()
+        self._pack_frozen_dgrad_weights()
+        self._frozen_folded = True
+
+    def _pack_frozen_dgrad_weights(self):
+        """The data-gradient weight layouts of frozen layers (rn_pack_conv_weight_dgrad_batch, rn_pack_depthwise_weight_flip)
+        are constants: packed here, when weights are loaded, from f32 copies of the model's variables in the compute
+        layout — frozen variables have no slice of the arenas — and never by refresh_dgrad_weights."""
+        lib, st, v = self.lib, _C.current_stream(), self.model.variables
+        if self.frozen_dgrad_packs:
+            arr = (_C.DgradPack * len(self.frozen_dgrad_packs))()
+            masters = []
+            for i, (kvar, k, cin, cout, cw, buf, mode) in enumerate(self.frozen_dgrad_packs):
+                masters.append(_hwio_to_ohwi(v[kvar].to(self.dev, torch.float32)))
+                arr[i].w_ohwi, arr[i].w_packed = masters[-1].data_ptr(), buf.data_ptr()
+                arr[i].R, arr[i].S, arr[i].Cin, arr[i].Cout, arr[i].Cout_pad, arr[i].pad_ = k, k, cin, cout, cw, mode
+            _C.check(lib.rn_pack_conv_weight_dgrad_batch(arr, len(self.frozen_dgrad_packs), st), "pack dgrad (frozen)")
+        for (kvar, k, C, buf) in self.frozen_dw_flip_packs:
+            w = v[kvar].to(self.dev, torch.float32).reshape(k * k, C).contiguous()
+            _C.check(lib.rn_pack_depthwise_weight_flip(w.data_ptr(), k, C, buf.data_ptr(), st), "pack dw flip (frozen)")
 
     def _fill_frozen_bn(self, groups=None):
         """(scale, shift) of the frozen BatchNorm layers under trainable convs, from the model's moving statistics by the
@@ -875,15 +961,17 @@ class TrainEngine:
                          self.folded.pixel_pair, _C.RN_ACT_NONE if raw_mode else None)
         for i, op in enumerate(ops):
             s = p.seg[i]
-            if raw_mode or self._conv_trainable(op):   # raw pre-BN output, or a live conv without BN (prediction convs)
+            if not self._conv_trainable(op):
+                self.folded.fill(s, op, self.t)
+                if raw_mode:     # frozen conv in front of a BatchNorm step (_bn_apart): weights and bias only
+                    s.scale = s.shift = s.residual = None
+            else:                # live conv: raw pre-BN output, or without BN (prediction convs)
                 s.w = self._weight_ptr(op["conv"])
                 s.bias = self._pview(op["conv"] + "/bias").data_ptr() if self.g.convs[op["conv"]]["bias"] else None
                 if not raw_mode:
                     s.residual = self.t[op["residual"]].data_ptr() if op.get("residual") else None
                 s.w_terms = self._f32_terms(op["conv"]) if op["conv"] in self.split_pack_of and op["conv"] not in self.pair_packs else 1
                 s.w_pair = 1 if op["conv"] in self.pair_packs else 0
-            else:
-                self.folded.fill(s, op, self.t)
             if self.folded.pixel_pair(op):      # algorithmic work: the layer's own
                 c, x, y = self.g.convs[op["conv"]], self._src(op["inp"]), dst_of(op)
                 self._algo[id(p)] = (2 * self.B * y.shape[1] * y.shape[2] * 9 * c["cin"] * c["cout"],
@@ -892,11 +980,18 @@ class TrainEngine:
         self.conv_launches.append((conv_launch_name("fwd:", ops, {n for n, _ in self.conv_launches}), p))
         return p
 
-    def _dw_problem(self, ops, dst_of):
+    def _dw_problem(self, ops, dst_of, folded=False):
         """forward depthwise launch over `ops` writing the raw (pre-BN) or final output; bf16 weights are
-        the plain-cast copies of the [k*k][C] masters."""
+        the plain-cast copies of the [k*k][C] masters, those of frozen layers the packed copies of _fold_frozen.
+        folded: frozen layers in inference form, BatchNorm and activation in the epilogue."""
+        live = self._conv_trainable(ops[0])
         p = dw_problem(self.g, ops, self.B, lambda o: self._src(o["inp"]), dst_of,
-                       lambda o: self.Pbf.data_ptr() + 2 * self.bf_off["dw:" + o["dw"]], _C.RN_ACT_NONE)
+                       (lambda o: self.Pbf.data_ptr() + 2 * self.bf_off["dw:" + o["dw"]]) if live else
+                       (lambda o: self.folded.packed[o["dw"]].data_ptr()),
+                       _C.ACT_IDS[ops[0]["act"]] if folded else _C.RN_ACT_NONE)
+        if folded:
+            for i, op in enumerate(ops):
+                self.folded.fill_dw(p.seg[i], op)
         self._keep.append(p)
         return p
 
@@ -947,9 +1042,11 @@ class TrainEngine:
         """BatchNorm problem over `ops` and its buffers (BnGroup).  With `conv_problem` (the launch that produces the raw outputs): the forward
         statistics' stage-1 partial sums are written by the conv epilogue (rn_conv_segment.bn_partial, one row per
         128 output pixels) and rn_bn_stats only does the final ordered reduction.
-        A frozen BatchNorm under a trainable conv (_bn_frozen) gets the same problem without anything the statistics, the
-        reductions or the gamma / beta gradients touch: y, z, residual, dz, dy, the gate bits and the constant fwd table."""
-        frozen = self._bn_frozen(ops[0])
+        A BatchNorm in inference mode (_bn_apart) gets the same problem without anything the statistics, the
+        reductions or the gamma / beta gradients touch: y, z, residual, dz, dy, the gate bits and the constant fwd table —
+        and without dy and the gate bits where nothing below the layer needs a gradient (the frozen project conv of a
+        drop_connect block: only its forward step runs)."""
+        frozen = self._bn_apart(ops[0])
         p = _C.BnProblem()
         p.num_segments = len(ops)
         p.act = _C.ACT_IDS[ops[0]["act"]]
@@ -967,10 +1064,11 @@ class TrainEngine:
             C = self.tensors[op["out"]][2]
             bn = op["bn"]
             y, z = self.raw[op["out"]], self.t[op["out"]]
-            dy = torch.empty_like(y)
+            backward = bool(self.requires.get(op["out"]))    # (always, but for a frozen layer above nothing that trains)
+            dy = torch.empty_like(y) if backward else None
             dys.append(dy)
             s = p.seg[i]
-            s.y, s.z, s.dy = y.data_ptr(), z.data_ptr(), dy.data_ptr()
+            s.y, s.z, s.dy = y.data_ptr(), z.data_ptr(), dy.data_ptr() if backward else None
             s.residual = self.t[op["residual"]].data_ptr() if op.get("residual") else None
             s.dz = self.grad[op["out"]].data_ptr() if op["out"] in self.grad else None
             s.dres = None
@@ -985,7 +1083,7 @@ class TrainEngine:
                 s.dgamma = self._pview(bn + "/gamma", self.G).data_ptr()
                 s.dbeta = self._pview(bn + "/beta", self.G).data_ptr()
             s.P, s.C, s.dres_accumulate = y.shape[0] * y.shape[1] * y.shape[2], C, 0
-            if (s.residual or frozen) and op["act"] in ("relu", "relu6"):
+            if (s.residual or frozen) and op["act"] in ("relu", "relu6") and backward:
                 # relu behind the residual add: the forward stores the gate as one bit per element, the two backward
                 # passes read P*C/8 bytes instead of z (rn_bn_segment.act_mask).  Every relu / relu6 layer of a frozen
                 # BatchNorm: rn_bn_frozen_bwd then reads the bits instead of y or z
@@ -1006,7 +1104,7 @@ class TrainEngine:
         if frozen:
             grp = BnGroup(p, None, None, None, dys, ops, fwd, True)
             self._fill_frozen_bn([grp])
-            self._keep += [p, fwd] + dys
+            self._keep += [p, fwd] + [dy for dy in dys if dy is not None]
             return grp
         fused = conv_problem is not None and self.fuse_bn_stats and conv_problem.out_dtype == _C.RN_DT_BF16
         if fused:
@@ -1039,6 +1137,9 @@ class TrainEngine:
         live_bn = bool(ops) and bool(self._bn_trainable(ops[0]))
         if any(bool(self._bn_trainable(o)) != live_bn for o in ops):
             raise NotImplementedError("a conv group mixes frozen and live BatchNorm")
+        if any(self._conv_trainable(o) != self._conv_trainable(ops[0]) for o in ops):
+            raise NotImplementedError(f"the {op['op']} group {op.get('group')} mixes frozen and live kernels: one launch "
+                                      "has one form, and no freeze pattern splits a group")
         return ops, live_bn
 
     def _bn_train_step(self, launch, ops, conv_problem=None):
@@ -1104,7 +1205,7 @@ class TrainEngine:
                 ops, live_bn = self._launch_ops_bn(op, done)
                 if not ops:
                     continue
-                if live_bn or self._bn_frozen(ops[0]):   # (frozen BatchNorm: no bn_partial epilogue in the conv)
+                if live_bn or self._bn_apart(ops[0]):   # (BatchNorm in inference mode: no bn_partial epilogue in the conv)
                     pc = self._conv_problem(ops, lambda o: self.raw[o["out"]], raw_mode=True)
                     self.fwd_steps.append(self._bn_train_step(lambda st, pc=pc: self._launch_conv(pc, st, "conv(train)"),
                                                               ops, conv_problem=pc if live_bn else None))
@@ -1116,18 +1217,29 @@ class TrainEngine:
                 ops, live_bn = self._launch_ops_bn(op, done)
                 if not ops:
                     continue
-                live_bn = live_bn or self._bn_frozen(ops[0])   # either way: raw output, then the BatchNorm step
-                pd = self._dw_problem(ops, (lambda o: self.raw[o["out"]]) if live_bn else (lambda o: self.t[o["out"]]))
+                live_bn = live_bn or self._bn_apart(ops[0])   # either way: raw output, then the BatchNorm step
+                # a frozen layer that hands no gradient down: BatchNorm and activation in the epilogue, as when serving
+                folded = not live_bn and not self._conv_trainable(ops[0]) and not self._passes_gradient(ops[0])
+                pd = self._dw_problem(ops, (lambda o: self.raw[o["out"]]) if live_bn else (lambda o: self.t[o["out"]]),
+                                      folded=folded)
                 self.dw_launches.append(("dw:" + (ops[0].get("group") or ops[0]["out"]), "fwd", pd, []))
                 prd = ctypes.byref(pd)
                 if live_bn:
                     self.fwd_steps.append(self._bn_train_step(
                         lambda st, prd=prd: _C.check(lib.rn_depthwise_conv2d_nhwc_fwd(prd, st), "depthwise(train)"), ops))
                 else:
-                    if ops[0].get("act") not in (None, "none"):
+                    if not folded and ops[0].get("act") not in (None, "none"):
                         raise NotImplementedError("depthwise conv with an activation but no BatchNorm")
                     self.fwd_steps.append(lambda st, prd=prd: _C.check(lib.rn_depthwise_conv2d_nhwc_fwd(prd, st),
                                                                        "depthwise"))
+            elif kind == "se" and not self._se_trainable(op):
+                # frozen, nothing below it trains (_analyse): the serving engine's in-place launch — no second tensor, no
+                # saved state; the out-of-place forward would write both only for a backward that never runs
+                x, se = self.t[op["inp"]], self.g.ses[op["se"]]
+                a = self.folded.se_args(op, x, B, self.se_ws)
+                self.se_launches.append(("se:" + op["out"], "fwd", B, x.shape[1] * x.shape[2], se["C"], se["se"]))
+                self.fwd_steps.append(lambda st, a=a: _C.check(lib.rn_squeeze_excite_inplace(*a, st),
+                                                               "rn_squeeze_excite_inplace"))
             elif kind == "se":
                 x, y = self.t[op["inp"]], self.t[op["out"]]
                 name, se = op["se"], self.g.ses[op["se"]]
@@ -1222,9 +1334,12 @@ class TrainEngine:
                 arr[i].w_ohwi, arr[i].w_packed = mptr, buf.data_ptr()
                 arr[i].R, arr[i].S, arr[i].Cin, arr[i].Cout, arr[i].Cout_pad, arr[i].pad_ = k, k, cin, cout, cw, mode
             self._dgrad_pack_items = arr
+        self._pack_frozen_dgrad_weights()    # (every later load re-enters it through _fold_frozen)
 
     def _plan_se_backward(self, op, joins):
         lib, B = self.lib, self.B
+        if not self._se_trainable(op):    # (frozen: in place in the forward pass, nothing below it trains)
+            return
         x, dy = self.t[op["inp"]], self.grad[op["out"]]
         dx = joins.sole(op["inp"], "se:" + op["out"])
         name, se = op["se"], self.g.ses[op["se"]]
@@ -1238,7 +1353,7 @@ class TrainEngine:
         self.se_launches.append(("se:" + op["out"], "bwd", B, x.shape[1] * x.shape[2], se["C"], se["se"]))
         self.bwd_steps.append(BackwardStep(
             lambda st, a=a: _C.check(lib.rn_squeeze_excite_bwd(*a, st), "rn_squeeze_excite_bwd"),
-            writes=[name + sfx for sfx in ("/conv2d/kernel", "/conv2d/bias", "/conv2d_1/kernel", "/conv2d_1/bias")]))
+            writes=[name + sfx for sfx in self._SE_VARS]))
 
     def _plan_maxpool_backward(self, op, joins):
         lib, B = self.lib, self.B
@@ -1296,6 +1411,8 @@ class TrainEngine:
     def _plan_topdown_backward(self, op, joins):
         lib, B = self.lib, self.B
         L = len(op["ins"])
+        if not any(self.requires.get(n) for n in op["outs"]):    # frozen inputs, frozen fusion weights: no backward
+            return
         if op["act"] == "swish":
             # rn_fpn_topdown_bwd_level refuses it: swish' needs the sum in front of the activation, and the
             # forward pass keeps only its output
@@ -1319,6 +1436,8 @@ class TrainEngine:
     def _plan_balance_backward(self, op, joins):
         lib, B = self.lib, self.B
         names = op["tensors"]
+        if not any(self.requires.get(n) for n in names):    # everything below BalanceFeatures is frozen
+            return
         dout = [self.grad["bal:" + n] for n in names]
         ins = [self.t[n] for n in names]
         din = [joins.sole(n, "balance") for n in names]
@@ -1655,18 +1774,17 @@ class TrainEngine:
     def _plan_conv_backward(self, ops, joins):
         """Backward of the conv launch over `ops`: gradient at the conv outputs (through the BatchNorm, or plain), weight and
         bias gradient of every distinct (shared) conv layer, data gradients."""
-        if not self._conv_trainable(ops[0]) and not any(self.requires.get(o["inp"]) for o in ops):
+        live = self._conv_trainable(ops[0])
+        if not live and not self._passes_gradient(ops[0]):
             return
-        if not self._conv_trainable(ops[0]):
-            raise NotImplementedError("backward through a frozen conv that sits above trainable layers")
         live_bn = bool(self._bn_trainable(ops[0]))
-        if live_bn or self._bn_frozen(ops[0]):
+        if live_bn or self._bn_apart(ops[0]):
             dy_of = self._plan_bn_backward(ops, joins)
         else:
             dy_of = self._plan_plain_dy(ops)
         self.dy_of.update(dy_of)
         by_conv = {}
-        for op in ops:
+        for op in ops if live else ():    # a frozen launch: the gradient at its outputs and the data gradients, no more
             by_conv.setdefault(op["conv"], []).append(op)
         for cname, cops in by_conv.items():
             self._plan_wgrad(cname, cops, dy_of)
@@ -1681,12 +1799,15 @@ class TrainEngine:
         shared separable conv); data gradient = the forward kernel on (zero-upsampled) dy with the
         tap-reversed filter, accumulating into gradient buffers that already hold a contribution."""
         lib, B = self.lib, self.B
-        if self._bn_trainable(ops[0]) or self._bn_frozen(ops[0]):
+        live = self._conv_trainable(ops[0])
+        if not live and not self._passes_gradient(ops[0]):
+            return
+        if self._bn_trainable(ops[0]) or self._bn_apart(ops[0]):
             dy_of = self._plan_bn_backward(ops, joins)
         else:
             dy_of = {op["out"]: self.grad[op["out"]] for op in ops}
         by_layer = {}
-        for op in ops:
+        for op in ops if live else ():    # a frozen launch: the data gradients only
             by_layer.setdefault(op["dw"], []).append(op)
         for dname, dops in by_layer.items():
             d = self.g.dws[dname]
@@ -1721,8 +1842,11 @@ class TrainEngine:
                 if op["dw"] not in flips:
                     buf = torch.empty((k * k, d["C"]), dtype=self.h16, device=self.dev)
                     flips[op["dw"]] = buf
-                    off, _ = self.p_off[d["kvar"]]
-                    self.dw_flip_packs.append((self.P.data_ptr() + 4 * off, k, d["C"], buf))
+                    if live:
+                        off, _ = self.p_off[d["kvar"]]
+                        self.dw_flip_packs.append((self.P.data_ptr() + 4 * off, k, d["C"], buf))
+                    else:         # a constant: _pack_frozen_dgrad_weights
+                        self.frozen_dw_flip_packs.append((d["kvar"], k, d["C"], buf))
                 src = dy_of[op["out"]]
                 x = self._src(op["inp"])
                 H, W = x.shape[1], x.shape[2]
@@ -1836,9 +1960,12 @@ class TrainEngine:
             if op["conv"] not in packs:
                 shape = (lib.rn_conv_cout_pad(4 * cin), 2, 2, cwp) if subpixel else (lib.rn_conv_cout_pad(cin), k, k, cwp)
                 packs[op["conv"]] = torch.empty(shape, dtype=self.h16, device=self.dev)
-                off, _ = self.p_off[c.get("kvar", op["conv"] + "/kernel")]
-                self.dgrad_packs.append((self.P.data_ptr() + 4 * off, k, cin, c["cout"], cwp, packs[op["conv"]],
-                                         1 if subpixel else 0))
+                kvar = c.get("kvar", op["conv"] + "/kernel")
+                if kvar in self.p_off:
+                    self.dgrad_packs.append((self.P.data_ptr() + 4 * self.p_off[kvar][0], k, cin, c["cout"], cwp,
+                                             packs[op["conv"]], 1 if subpixel else 0))
+                else:             # frozen conv: a constant, packed when weights are loaded (_pack_frozen_dgrad_weights)
+                    self.frozen_dgrad_packs.append((kvar, k, cin, c["cout"], cwp, packs[op["conv"]], 1 if subpixel else 0))
             x = self._src(op["inp"])
             H, W = x.shape[1], x.shape[2]
             gbuf, accumulate = joins.add(op["inp"], name)
