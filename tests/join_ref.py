@@ -42,11 +42,12 @@ LIMITS = dict(cos=0.9999, o2=2e-2, o4=5e-3)   # test_bottleneck_tail_forward_bac
 
 
 # ---- the comparison ------------------------------------------------------------------------------------------------------
-def figures(got, want64):
-    """(cosine, fraction beyond 2 ulp, fraction beyond 4 ulp) of a gradient buffer against its float64 restatement"""
+def figures(got, want64, mantissa_bits=7):
+    """(cosine, fraction beyond 2 ulp, fraction beyond 4 ulp) of a gradient buffer against its float64 restatement;
+    mantissa_bits: of the ulp (ulp_ref._ulp_outliers)"""
     a, b = got.detach().to("cpu").double().reshape(-1), want64.detach().to("cpu").double().reshape(-1)
     cos = (a @ b / (a.norm() * b.norm() + 1e-300)).item()
-    return cos, _ulp_outliers(a, b, 2.0), _ulp_outliers(a, b, 4.0)
+    return cos, _ulp_outliers(a, b, 2.0, mantissa_bits), _ulp_outliers(a, b, 4.0, mantissa_bits)
 
 
 def accept(fig, n, limits=LIMITS):
@@ -148,6 +149,11 @@ def conv_output(eng, op, x):
     c = eng.g.convs[op["conv"]]
     w = _r(_var(eng, c.get("kvar", op["conv"] + "/kernel"), dt).permute(3, 2, 0, 1), h)   # HWIO -> OIHW
     b = _var(eng, op["conv"] + "/bias", dt) if c["bias"] else None
+    if op["op"] == "stem":      # first-layer conv: the image's own pads (7x7 / 2: 3 and 3; EfficientNet's 3x3 / 2: TF SAME)
+        k, s, pt, pl = op.get("k", 7), c["stride"], op.get("pad_top", 3), op.get("pad_left", 3)
+        Ho, Wo = eng.tensors[op["out"]][:2]
+        pb, pr = max((Ho - 1) * s + k - x.shape[1] - pt, 0), max((Wo - 1) * s + k - x.shape[2] - pl, 0)
+        return _nhwc(F.conv2d(F.pad(_nchw(x), (pl, pr, pt, pb)), w, b, stride=s))
     return _nhwc(F.conv2d(_nchw(x), w, b, stride=c["stride"], padding=op["pad"]))
 
 
