@@ -763,6 +763,44 @@ int rn_optim_sgd_step(float* params, const float* grads, float* momentum_buf, fl
                       const void* segs_dev, const int32_t* block_seg_dev, int num_blocks, float lr, float momentum,
                       float ema_decay, int nesterov, const float* skip_flag, void* stream);
 
+/*
+ * Per-variable statistics of an arena: the reference's --enable_weights_info (executor.py:329-344: tf.norm of every
+ * trainable variable at each logging point, a tf.summary.histogram of each every 50 executions), over the segment
+ * table and blocks above.  Of the segs_dev record only offset, size, block_begin and nblocks are read.  The arena is
+ * read only, each element of each segment once per call, 16 bytes per lane where the block's fp32 offset is a multiple
+ * of 4, a scalar tail, a scalar loop for other offsets.  Never read and never counted: the 4 reserved floats at the
+ * front, the padding between segments, anything past the last segment.
+ *   rn_arena_stats     stats[s] = {norm, min, max}, nonfinite[s], for every segment s.
+ *       norm = sqrtf(sum of x * x) over all `size` elements.  Each square and each sum of a lane's running total is one
+ *              rounded fp32 operation (at most rn_optim_chunk() / 256 + 1 additions in a chain); lanes, waves and blocks
+ *              are then summed in fp64 — per-block partials in the workspace, one wave per segment adding its blocks in a
+ *              fixed order and tree — and the root is taken in fp64 and rounded to fp32.  No floating-point atomics: the
+ *              same bits on every run and every stream.  A NaN element gives NaN; an infinite element (or a square
+ *              beyond fp32, |x| > 1.8e19, as with tf.norm) and no NaN gives +inf.
+ *       min, max over the finite elements only, exact, subnormals kept; nonfinite = the number of NaN or +-inf elements.
+ *              A segment without a finite element reports min = max = 0.
+ *   rn_arena_histogram counts[s][b]: the bucket rule of TensorBoard's `histogram` summary (bucket_count = num_buckets,
+ *       30 in the reference) over the FINITE elements, with min and max as rn_arena_stats wrote them to `stats`:
+ *           max == min:  every finite element goes to bucket num_buckets - 1
+ *           otherwise:   width = (double(max) - double(min)) / num_buckets
+ *                        b = min(num_buckets - 1, (int)floor((double(x) - double(min)) / width))
+ *       in fp64, one rounding per operation, a true division: numpy float64 gives the same integers.  The bucket edges
+ *       are linspace(min, max, num_buckets + 1).  Non-finite elements are counted in nonfinite, not here (TensorBoard
+ *       lets them poison the edges): sum_b counts[s][b] + nonfinite[s] == size.  counts is cleared in-stream by the
+ *       call, then filled with integer atomics: per-wave LDS buckets, one global add per workgroup and non-empty bucket.
+ *       The index is clamped into 0 .. num_buckets - 1 whatever `stats` holds.
+ * RN_EINVAL before any launch, outputs untouched: a null pointer, num_segments <= 0, num_blocks <= 0, num_buckets outside
+ * 1..64.  RN_ENOMEM: a workspace smaller than rn_arena_stats_workspace_bytes.
+ */
+size_t rn_arena_stats_workspace_bytes(int num_blocks, int num_segments);
+int rn_arena_stats(const float* arena, const void* segs_dev, int num_segments, const int32_t* block_seg_dev,
+                   int num_blocks, float* stats /* dev f32 [num_segments][3]: norm, min, max */,
+                   int32_t* nonfinite /* dev i32 [num_segments] */, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int rn_arena_histogram(const float* arena, const void* segs_dev, int num_segments, const int32_t* block_seg_dev,
+                       int num_blocks, const float* stats /* as written by rn_arena_stats */, int num_buckets,
+                       int32_t* counts /* dev i32 [num_segments][num_buckets], overwritten */, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * C1-C3  collectives of the data-parallel step over RCCL / xGMI (the reference reaches them through
  * tf.distribute: retinanet_loss.py:46-49, model/utils.py:10-12, executor.py:436-437).  One process per GPU; rank 0

@@ -44,6 +44,12 @@ int rn_validate_launch_opts(const rn_launch_opts& opts, const char* who);
 static inline int64_t rn_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t rn_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// ---- the flat fp32 parameter arena (rn_optim.hip, rn_stats.hip) -------------------------------------------------
+// A tensor is a segment; a block of OPT_CHUNK elements belongs to exactly one segment (block_seg_dev: block -> segment).
+// The record of segs_dev, as include/rnet_hip.h describes it.
+#define OPT_CHUNK 8192  // elements per block
+struct OptSeg { long long offset, size; int wd, block_begin, nblocks, pad_; long long bf16_offset; };
+
 // ---- the 16-bit storage type of activations and packed weights -------------------------------------------------
 // The library is built twice from the same sources: librnet_hip.so with bfloat16 storage (the `mixed_bfloat16`
 // policy of the reference's TPU / bf16 configs, __main__.py:76-77) and, with -DRN_F16, librnet_hip_f16.so with IEEE

@@ -14,10 +14,7 @@
 // Deterministic: block partials are added in index order.  HBM-bound: 34.4 M params.
 #include "rn_common.h"
 
-#define OPT_THREADS 256
-#define OPT_CHUNK 8192  // elements per block
-
-struct OptSeg { long long offset, size; int wd, block_begin, nblocks, pad_; long long bf16_offset; };
+#define OPT_THREADS 256   // (OPT_CHUNK and OptSeg: rn_common.h, shared with rn_stats.hip)
 
 // partial[b] = sum of squares of the block's (unscaled, weight-decayed) gradients; partial_w[b] = sum of squares of
 // its weights when the tensor is weight-decayed (the l2-regularization term the reference logs, executor.py:296-299)

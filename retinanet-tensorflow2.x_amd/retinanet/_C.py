@@ -22,7 +22,7 @@ RN_ACT_NONE, RN_ACT_RELU, RN_ACT_RELU6, RN_ACT_SWISH = 0, 1, 2, 3
 RN_FUSION_FAST_ATTENTION, RN_FUSION_FAST_CHANNEL_ATTENTION = 1, 2
 FUSION_IDS = {"fast_attention": RN_FUSION_FAST_ATTENTION, "fast_channel_attention": RN_FUSION_FAST_CHANNEL_ATTENTION}
 RN_CONV_MAX_SEGMENTS = 10
-ABI_VERSION = 15
+ABI_VERSION = 16
 RN_OPT_ADAM, RN_OPT_RMSPROP, RN_OPT_ADAGRAD, RN_OPT_SGD = 1, 2, 3, 4                   # rn_optim_rule.rule
 RN_OPT_AMSGRAD, RN_OPT_CENTERED, RN_OPT_MOMENTUM, RN_OPT_NESTEROV = 1, 2, 4, 8         # rn_optim_rule.flags
 # f32 kernels of the dtype=float32 prediction convs (detection_head.py:80-88) as split-bf16 planes (rn_conv_segment.w_terms)
@@ -261,6 +261,10 @@ _SIGNATURES = {
                                   c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
     "rn_optim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_int, POINTER(OptimRule), c_void_p, c_void_p]),
+    "rn_arena_stats_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rn_arena_stats": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                               c_void_p]),
+    "rn_arena_histogram": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "rn_prepare_image": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, POINTER(c_float),
                                  POINTER(c_float), c_float, c_void_p]),
     "rn_bottleneck64_supported": (c_int, [c_int, c_int, c_int, c_int]),

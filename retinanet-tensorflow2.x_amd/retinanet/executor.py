@@ -13,7 +13,8 @@ Same constructor, same `run()` dispatch, same step / checkpoint / evaluation sem
   * `evaluate()` (:477-552): moving-average weights in, `_eval_step` over `val_steps` batches, COCOEvaluator, weights back.
 What the MI355X build does differently, by design: one PROCESS per GPU (`strategy` is `retinanet.distribute.Strategy`, not a
 tf.distribute strategy), so every rank owns its input pipeline shard; scalars go to `<tensorboard_dir>/<name>/{train,eval}/
-scalars.jsonl` (TensorBoard event files, the TF profiler hooks, the graph trace and the Discord hook are the reference's
+scalars.jsonl`, with `enable_weights_info` the per-variable norms and histograms to `train/weights.jsonl` and
+`train/histograms.jsonl` beside it (executor.py:329-344) (TensorBoard event files, the TF profiler hooks, the graph trace and the Discord hook are the reference's
 control plane — out of scope)."""
 from __future__ import annotations
 
@@ -102,6 +103,11 @@ class _ScalarWriter:
         self._fp.write(json.dumps({"step": int(step), **{k: float(v) for k, v in values.items()}}) + "\n")
         self._fp.flush()
 
+    def row(self, values):
+        """one JSON object per line, values as they are (lists, strings, ints)"""
+        self._fp.write(json.dumps(values) + "\n")
+        self._fp.flush()
+
 
 def _f(v):
     return float(v.item()) if hasattr(v, "item") else float(v)
@@ -143,6 +149,7 @@ class Executor:
         self._current_trial = 1
         self._engine = None
         self._loaded_slots = {}
+        self._warned_nonfinite = False
         if params.training.recovery.use_inflection_detector:
             self._inflection_detector = InflectionDetector(name=params.training.recovery.metric_key,
                                                            threshold=params.training.recovery.threshold)
@@ -253,6 +260,30 @@ class Executor:
                     (key == "eval" and self.run_mode == "continuous_eval"):
                 self._summary_writers.setdefault(key, _ScalarWriter(os.path.join(self.summary_dir, self.name, sub,
                                                                                  "scalars.jsonl")))
+
+    def _write_weights_info(self, step, write_histogram=False):
+        """--enable_weights_info (executor.py:329-344): `weights/<variable>_norm` of every trainable variable as one row of
+        train/weights.jsonl and, write_histogram, one row per variable in train/histograms.jsonl (the bucket edges are
+        numpy.linspace(min, max, len(counts) + 1); NaN / inf elements are counted in `nonfinite`, not in a bucket).  One call
+        of TrainEngine.weights_info: two or three launches and one device -> host copy for all variables."""
+        info = self._engine.weights_info(histogram=write_histogram)
+        names = info["names"]
+        train_dir = os.path.join(self.summary_dir, self.name, "train")
+        for key in ("weights", "histograms")[:2 if write_histogram else 1]:
+            if "train-" + key not in self._summary_writers:
+                self._summary_writers["train-" + key] = _ScalarWriter(os.path.join(train_dir, key + ".jsonl"))
+        self._summary_writers["train-weights"].row(
+            {"step": int(step), **{"weights/{}_norm".format(k): float(v) for k, v in zip(names, info["norm"])}})
+        if write_histogram:
+            for i, k in enumerate(names):
+                self._summary_writers["train-histograms"].row(
+                    {"step": int(step), "name": k, "min": float(info["min"][i]), "max": float(info["max"][i]),
+                     "nonfinite": int(info["nonfinite"][i]), "counts": [int(c) for c in info["counts"][i]]})
+        bad = [k for k, c in zip(names, info["nonfinite"]) if c]
+        if bad and not self._warned_nonfinite:
+            self._warned_nonfinite = True
+            logging.warning("Non-finite values in %d trainable variables at step %d, first: %s (%d of its elements)",
+                            len(bad), int(step), bad[0], int(info["nonfinite"][names.index(bad[0])]))
 
     # ---- checkpoints (executor.py:221-257) ---------------------------------------------------------------------
     def _restore_checkpoint(self, checkpoint=None):
@@ -536,6 +567,9 @@ class Executor:
                 self._save("weights_step_{}".format(current_step))
             if "train" in self._summary_writers:
                 self._summary_writers["train"].scalars(current_step, loss_dict)
+            if self.enable_weights_info and self._is_chief:
+                self._write_weights_info(current_step,
+                                         write_histogram=current_step % (50 * self.steps_per_execution) == 0)
             logging.info("[trial: %d/%d][global_step %d/%d][ETA: %s][%.2f imgs/s] %s", self._current_trial,
                          self._max_trials, current_step, self.train_steps, eta, sps * self.batch_size["train"],
                          {k: float(np.round(v, 4)) for k, v in loss_dict.items()})

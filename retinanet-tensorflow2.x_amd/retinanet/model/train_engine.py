@@ -250,6 +250,7 @@ class TrainEngine:
         self.loss_scale = None    # LossScaleOptimizer state (mixed_float16 configs): see optimizer_step
         self._ls_host = self._ls_event = None   # pinned copy of the "gradients not finite" flag and its event
         self._ls_pending = False  # that copy has not been looked at yet (_resolve_loss_scale)
+        self._wi = None           # weights_info(): workspace, device results, pinned results — made on first use
         self._train_step_active = False
         self._micro_next = 0      # the micro-step accumulate_micro_step expects next (accumulation_steps > 1)
         self._micro_scale = 1.0   # the loss scale of the optimizer step under way: one for all its micro-steps
@@ -2260,6 +2261,42 @@ class TrainEngine:
         """Host-side state of the last train_step (loss scale, optimizer.iterations) brought up to date: call before
         reading them between steps (the executor does after each execution; state_dict does)."""
         self._resolve_loss_scale()
+
+    def weights_info(self, histogram=False, bucket_count=30):
+        """The reference's --enable_weights_info (executor.py:329-344) for every trainable variable at once: tf.norm, the
+        finite minimum / maximum, the count of NaN / inf elements and, histogram=True, TensorBoard's `bucket_count` buckets
+        over linspace(min, max, bucket_count + 1) (rn_arena_stats / rn_arena_histogram, include/rnet_hip.h).  Reads the fp32
+        master weights P — not the moving average, not the 16-bit copies — in the stream that ordered the last optimizer
+        step; writes no arena and touches no planned launch.  One device -> host copy per call.
+        -> {"names": train_names, "norm" f32[n], "min" f32[n], "max" f32[n], "nonfinite" i32[n], "counts" i32[n, buckets] | None}"""
+        if not 1 <= int(bucket_count) <= 64:
+            raise ValueError(f"weights_info: bucket_count {bucket_count} is outside 1..64")
+        lib, n, nb = self.lib, self.n_segs, int(bucket_count)
+        self.finish_step()
+        with torch.cuda.device(self.dev):
+            if self._wi is None:
+                ws = torch.empty((lib.rn_arena_stats_workspace_bytes(self.n_blocks, n),), dtype=torch.uint8, device=self.dev)
+                # one i32 result arena, so that one copy brings everything over: [n][3] stats (f32 bits), [n] nonfinite,
+                # [n][64] counts (the first n * bucket_count of them are in use)
+                out = torch.zeros((n * (4 + 64),), dtype=torch.int32, device=self.dev)
+                self._wi = (ws, out, torch.empty((n * (4 + 64),), dtype=torch.int32, pin_memory=True))
+            ws, out, host = self._wi
+            st = _C.current_stream()
+            stats, bad, counts = out.data_ptr(), out.data_ptr() + 12 * n, out.data_ptr() + 16 * n
+            _C.check(lib.rn_arena_stats(self.P.data_ptr(), self.segs_dev.data_ptr(), n, self.block_seg_dev.data_ptr(),
+                                        self.n_blocks, stats, bad, ws.data_ptr(), ws.numel(), st), "rn_arena_stats")
+            if histogram:
+                _C.check(lib.rn_arena_histogram(self.P.data_ptr(), self.segs_dev.data_ptr(), n,
+                                                self.block_seg_dev.data_ptr(), self.n_blocks, stats, nb, counts, st),
+                         "rn_arena_histogram")
+            used = n * (4 + (nb if histogram else 0))
+            host[:used].copy_(out[:used], non_blocking=True)
+            torch.cuda.current_stream(self.dev).synchronize()
+        res = host[:used].numpy().copy()
+        s = res[:3 * n].view(np.float32).reshape(n, 3)
+        return {"names": list(self.train_names), "norm": s[:, 0].copy(), "min": s[:, 1].copy(), "max": s[:, 2].copy(),
+                "nonfinite": res[3 * n:4 * n].copy(),
+                "counts": res[4 * n:].reshape(n, nb).copy() if histogram else None}
 
     def train_step(self, images, targets):
         """(images f32[B,H,W,3], targets from LabelEncoder.encode_batch) -> the loss dict of Executor._train_step
