@@ -417,6 +417,76 @@ int rn_pack_image_nhwc4(const float* images, int N, int H, int W, int pad_top, i
                         void* packed, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * INT8 serving of the detection heads (rn_conv_i8.hip; DESIGN.md "INT8 serving").  Symmetric quantisation: the int8
+ * value 0 is the real value 0, every tensor lives in [-127, 127].
+ *
+ * rn_conv3x3_i8_fwd: grouped implicit-GEMM convolution, 3x3 / stride 1 / pad 1 (zero padding), int32 accumulation on
+ * v_mfma_i32_32x32x32_i8.  Up to RN_CONV_MAX_SEGMENTS segments per launch, each with its own shapes and epilogue
+ * vectors.  x int8 dense NHWC [N,H,W,Cin]; w int8 packed by rn_pack_conv_weight_i8; y int8 or f32 dense [N,H,W,Cout].
+ * Epilogue, every step a separately rounded fp32 operation (no fused multiply-add):
+ *   t = (float)acc * mul[c];   t = t + add[c];   t = act(t)   (none | relu | relu6)
+ *   out_dtype RN_DT_I8:  y = (int8) clamp(rintf(t * out_inv_scale), -127, 127)
+ *   out_dtype RN_DT_F32: y = t
+ * Accepted: Cin % 64 == 0, 64 <= Cin <= 512 (|acc| <= 9 * 512 * 127^2 < 2^31), any Cout >= 1, x and w 16-byte aligned.
+ * RN_EINVAL before anything is launched for everything else (swish included).  No host read, no allocation: the
+ * launch can be captured in a HIP graph. */
+enum { RN_DT_I8 = 2 };
+
+typedef struct {
+  const void* x;       /* int8 [N,H,W,Cin] */
+  const void* w;       /* int8, rn_pack_conv_weight_i8 */
+  void* y;             /* int8 or f32 [N,H,W,Cout] */
+  const float* mul;    /* f32[Cout] */
+  const float* add;    /* f32[Cout] */
+  float out_inv_scale; /* RN_DT_I8 outputs: 1 / (scale of y) */
+  int32_t N, H, W, Cin, Cout;
+} rn_conv_i8_segment;
+
+typedef struct {
+  int32_t act;       /* RN_ACT_NONE | RN_ACT_RELU | RN_ACT_RELU6 */
+  int32_t out_dtype; /* RN_DT_I8 or RN_DT_F32 */
+  int32_t num_segments;
+  int32_t pad_;
+  rn_conv_i8_segment seg[RN_CONV_MAX_SEGMENTS];
+} rn_conv_i8_problem;
+
+int rn_conv3x3_i8_fwd(const rn_conv_i8_problem* problem /* host */, void* stream);
+/* bytes of the packed int8 weights of a 3x3 layer: [Cout rounded up to 128][3][3][Cin], pad rows zero */
+size_t rn_conv_i8_weight_bytes(int Cin, int Cout);
+/* f32 3x3 weights (layout_ohwi = 0: HWIO, 1: [Cout][R][S][Cin]) -> per-output-channel symmetric int8:
+ * w_scale[c] = max|w[..c]| / 127 (1 when that maximum is 0), q = clamp(rintf(w / w_scale[c]), -127, 127). */
+int rn_pack_conv_weight_i8(const float* w, int layout_ohwi, int Cin, int Cout, void* w_packed, float* w_scale,
+                           void* stream);
+
+/* One launch quantises up to RN_CONV_MAX_SEGMENTS tensors of the 16-bit storage type to dense int8 NHWC:
+ * q = clamp(rintf((float)x * inv_scale), -127, 127).  pix_stride >= C elements between pixels of x. */
+typedef struct {
+  const void* x;   /* 16-bit [pixels, pix_stride] */
+  void* y;         /* int8 [pixels, C] */
+  int64_t pixels;
+  int32_t C, pix_stride;
+  float inv_scale;
+  int32_t pad_;
+} rn_quant_segment;
+
+typedef struct {
+  int32_t num_segments;
+  int32_t pad_;
+  rn_quant_segment seg[RN_CONV_MAX_SEGMENTS];
+} rn_quant_problem;
+
+int rn_quantize_i8(const rn_quant_problem* problem /* host */, void* stream);
+
+/* Calibration statistics of a 16-bit tensor [pixels, pix_stride] (the first C channels of every pixel); both
+ * ACCUMULATE into their device output across calls (zero it once).
+ * rn_calib_absmax:    *amax = max(*amax, max|x|)  (device f32; non-negative floats order like their bit patterns)
+ * rn_calib_histogram: counts[min((int)(|x| * (2048 / range)), 2047)] += 1  (device int64[RN_CALIB_BINS]; the
+ *                     quotient 2048 / range and the product are fp32), range > 0. */
+#define RN_CALIB_BINS 2048
+int rn_calib_absmax(const void* x, int64_t pixels, int C, int pix_stride, float* amax, void* stream);
+int rn_calib_histogram(const void* x, int64_t pixels, int C, int pix_stride, float range, int64_t* counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Backward of K1/K2 (the tape.gradient of executor.py:427-428 through Conv2D).
  * Weight gradient: dw f32 [Cout][R][S][Cin] (the packed compute layout) = beta*dw + sum over
  * all segments' output pixels of dy[p][co] * x[shifted pixel][ci].  Segments share one weight

@@ -16,13 +16,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RNET_HIP_LIB") or os.path.join(_HERE, "librnet_hip.so")
 LIB_PATH_F16 = os.environ.get("RNET_HIP_LIB_F16") or os.path.join(_HERE, "librnet_hip_f16.so")
 
-RN_DT_F32, RN_DT_BF16 = 0, 1
+RN_DT_F32, RN_DT_BF16, RN_DT_I8 = 0, 1, 2
+RN_CALIB_BINS = 2048
 RN_OK, RN_EINVAL, RN_ENOMEM, RN_EHIP, RN_ECOMM, RN_EUNSUPPORTED = 0, -1, -2, -3, -4, -5   # rn_status
 RN_ACT_NONE, RN_ACT_RELU, RN_ACT_RELU6, RN_ACT_SWISH = 0, 1, 2, 3
 RN_FUSION_FAST_ATTENTION, RN_FUSION_FAST_CHANNEL_ATTENTION = 1, 2
 FUSION_IDS = {"fast_attention": RN_FUSION_FAST_ATTENTION, "fast_channel_attention": RN_FUSION_FAST_CHANNEL_ATTENTION}
 RN_CONV_MAX_SEGMENTS = 10
-ABI_VERSION = 16
+ABI_VERSION = 17
 RN_OPT_ADAM, RN_OPT_RMSPROP, RN_OPT_ADAGRAD, RN_OPT_SGD = 1, 2, 3, 4                   # rn_optim_rule.rule
 RN_OPT_AMSGRAD, RN_OPT_CENTERED, RN_OPT_MOMENTUM, RN_OPT_NESTEROV = 1, 2, 4, 8         # rn_optim_rule.flags
 # f32 kernels of the dtype=float32 prediction convs (detection_head.py:80-88) as split-bf16 planes (rn_conv_segment.w_terms)
@@ -88,6 +89,26 @@ class ConvProblem(Structure):
                 ("pad_top", c_int32), ("pad_left", c_int32), ("act", c_int32), ("out_dtype", c_int32),
                 ("num_segments", c_int32), ("seg", ConvSegment * RN_CONV_MAX_SEGMENTS), ("opts", LaunchOpts),
                 ("splitk_ws", c_void_p), ("splitk_ws_bytes", c_int64)]
+
+
+class ConvI8Segment(Structure):   # rn_conv_i8_segment
+    _fields_ = [("x", c_void_p), ("w", c_void_p), ("y", c_void_p), ("mul", c_void_p), ("add", c_void_p),
+                ("out_inv_scale", c_float), ("N", c_int32), ("H", c_int32), ("W", c_int32), ("Cin", c_int32),
+                ("Cout", c_int32)]
+
+
+class ConvI8Problem(Structure):   # rn_conv_i8_problem
+    _fields_ = [("act", c_int32), ("out_dtype", c_int32), ("num_segments", c_int32), ("pad_", c_int32),
+                ("seg", ConvI8Segment * RN_CONV_MAX_SEGMENTS)]
+
+
+class QuantSegment(Structure):   # rn_quant_segment
+    _fields_ = [("x", c_void_p), ("y", c_void_p), ("pixels", c_int64), ("C", c_int32), ("pix_stride", c_int32),
+                ("inv_scale", c_float), ("pad_", c_int32)]
+
+
+class QuantProblem(Structure):   # rn_quant_problem
+    _fields_ = [("num_segments", c_int32), ("pad_", c_int32), ("seg", QuantSegment * RN_CONV_MAX_SEGMENTS)]
 
 
 class WgradSegment(Structure):
@@ -200,6 +221,12 @@ _SIGNATURES = {
     "rn_pack_conv_weight_pair": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "rn_pack_conv_weight_split": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                           c_void_p]),
+    "rn_conv3x3_i8_fwd": (c_int, [POINTER(ConvI8Problem), c_void_p]),
+    "rn_conv_i8_weight_bytes": (c_size_t, [c_int, c_int]),
+    "rn_pack_conv_weight_i8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rn_quantize_i8": (c_int, [POINTER(QuantProblem), c_void_p]),
+    "rn_calib_absmax": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "rn_calib_histogram": (c_int, [c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_void_p]),
     "rn_pack_stem_weight": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "rn_stem_padded_width": (c_int, [c_int]),
     "rn_pack_stem_input": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

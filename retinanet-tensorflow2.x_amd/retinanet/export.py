@@ -10,7 +10,8 @@ this build replaces.  What is exported instead, under `<export_dir>/<experiment.
   config.json                      the config (as export.py:163 dumps it)
   <mode>/weights.safetensors       every variable under its Keras name, conv kernels HWIO float32 (moving averages
                                    swapped in unless --ignore_moving_average_weights)
-  <mode>/signatures.json           the two signatures' input / output specs
+  <mode>/signatures.json           the two signatures' input / output specs (+ "precision": "int8" for an INT8 export)
+  <mode>/quantization.json         --precision int8 only: calibration method, image count and the per-tensor scales
 and `retinanet.export.load(<export_dir>/<name>/<mode>)` returns an object whose `.signatures['serving_default']` /
 `.signatures['prepare_image']` are callables with the reference's keyword argument (`image=`) and output dicts, running
 the HIP engines (the forward pass + post-processing of `serving_default` replays as ONE captured HIP graph).
@@ -44,12 +45,14 @@ def define_flags():
     f.DEFINE_boolean("skip_prepare_image_fn", False, "Skip exporting `prepare_image` signature")
     f.DEFINE_boolean("debug", False, "Print debugging info")
     f.DEFINE_string("log_dir", None, "absl's log directory flag")
-    # TensorRT calibration flags of the reference: accepted so that existing command lines parse
+    # the reference's INT8 calibration flags (export.py:79-104).  --precision int8 with --mode tf calibrates the detection
+    # heads on images from --calibration_images_dir and serves them on the int8 kernels (retinanet/model/quantization.py);
+    # fp32 (the default) and fp16 export the bf16 / f16 engines as before
     f.DEFINE_string("calibration_images_dir", "coco/val2017", "Calibration images dir")
     f.DEFINE_enum("calibration_method", "entropy", ["entropy", "minmax"], "INT8 Calibration method")
     f.DEFINE_integer("calibration_batch_size", 8, "Batch size for calibration")
     f.DEFINE_integer("num_calibration_images", 5000, "Number of images used in calibration")
-    f.DEFINE_string("precision", "fp32", "Execution precision for TensorRT Engines")
+    f.DEFINE_string("precision", "fp32", "Execution precision: fp32 | fp16 (the 16-bit engines) | int8 (calibrated heads)")
     return f
 
 
@@ -66,7 +69,9 @@ def signature_specs(params, with_prepare_image=True):
     return specs
 
 
-def write_saved_model(model, params, out_dir, mode="tf", with_prepare_image=True):
+def write_saved_model(model, params, out_dir, mode="tf", with_prepare_image=True, quantization=None):
+    """quantization: a QuantizationTable — written as quantization.json, and `"precision": "int8"` recorded in
+    signatures.json, which makes `load()` build the INT8 engine"""
     from safetensors.torch import save_file
     if mode != "tf":
         raise NotImplementedError(f"export mode {mode!r} needs TF-TRT / tf2onnx / TensorRT: out of scope on MI355X")
@@ -76,9 +81,13 @@ def write_saved_model(model, params, out_dir, mode="tf", with_prepare_image=True
     os.makedirs(out_dir)
     save_file({k: v.detach().cpu().contiguous() for k, v in model.variables.items()},
               os.path.join(out_dir, "weights.safetensors"))
+    meta = {"format": "retinanet-mi355x-saved-model", "version": 1, "mode": mode,
+            "signatures": signature_specs(params, with_prepare_image)}
+    if quantization is not None:
+        quantization.save(os.path.join(out_dir, "quantization.json"))
+        meta["precision"] = "int8"
     with open(os.path.join(out_dir, "signatures.json"), "w") as f:
-        json.dump({"format": "retinanet-mi355x-saved-model", "version": 1, "mode": mode,
-                   "signatures": signature_specs(params, with_prepare_image)}, f, indent=2)
+        json.dump(meta, f, indent=2)
     with open(os.path.join(out_dir, "config.json"), "w") as f:
         f.write(json.dumps(params, indent=4))
     return out_dir
@@ -101,7 +110,11 @@ class SavedModel:
         builder = ModelBuilder(self.params, run_mode="export", device=device)
         self.model = builder()
         self.model.load_weights(os.path.join(path, "weights.safetensors"))
-        self._infer = builder.prepare_model_for_export(self.model, mode=self.meta["mode"])
+        self.quantization = None
+        if self.meta.get("precision") == "int8":
+            from retinanet.model.quantization import QuantizationTable
+            self.quantization = QuantizationTable.load(os.path.join(path, "quantization.json"))
+        self._infer = builder.prepare_model_for_export(self.model, mode=self.meta["mode"], quantization=self.quantization)
         self._pre = PreprocessingPipeline(self.params.input.input_shape, self.params.dataloader_params)
         spec = self.meta["signatures"]
         shape = tuple(spec["serving_default"]["inputs"]["image"]["shape"])
@@ -169,7 +182,18 @@ def main(argv=None):
         with_pre = not FLAGS.skip_prepare_image_fn and "tf" in FLAGS.mode
         if not with_pre:
             logging.warning("Skipping `prepare_image` signature in `saved_model`")
-        write_saved_model(executor.model, params, saved_model_export_dir, mode=FLAGS.mode, with_prepare_image=with_pre)
+        quantization = None
+        if FLAGS.precision not in ("fp32", "fp16", "int8"):
+            raise ValueError(f"--precision {FLAGS.precision!r}: one of fp32, fp16, int8")
+        if FLAGS.precision == "int8" and FLAGS.mode == "tf":
+            from retinanet.model.quantization import calibrate_from_directory
+            logging.info("Calibrating the detection heads (%s) on up to %d images from %s", FLAGS.calibration_method,
+                         FLAGS.num_calibration_images, FLAGS.calibration_images_dir)
+            quantization = calibrate_from_directory(executor.model, params, FLAGS.calibration_images_dir,
+                                                    FLAGS.num_calibration_images, FLAGS.calibration_batch_size,
+                                                    FLAGS.calibration_method)
+        write_saved_model(executor.model, params, saved_model_export_dir, mode=FLAGS.mode, with_prepare_image=with_pre,
+                          quantization=quantization)
         for name, spec in signature_specs(params, with_pre).items():
             logging.info("\nSignature: %s\n Input Shapes:\n %s\nOutput Shapes:\n%s", name,
                          {k: v["shape"] for k, v in spec["inputs"].items()},

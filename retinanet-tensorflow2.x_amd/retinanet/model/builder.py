@@ -171,18 +171,20 @@ class RetinaNetModel:
             with torch.cuda.device(self.device):
                 eng.load_variables(self.variables)
 
-    def inference_engine(self, batch_size, capture_graph=False, serving=False):
+    def inference_engine(self, batch_size, capture_graph=False, serving=False, quantization=None):
         """serving=True: the engine behind `serving_default` / export — without the auxiliary IoU head, whose output
         the post-processing stage never reads (model/builder.py:153-185); the same engine when the model has none."""
         serving = bool(serving) and "iou-predictions" in self.graph.outputs
         key = (int(batch_size), bool(capture_graph)) + (("serving",) if serving else ())
+        if quantization is not None:   # a QuantizationTable: the heads on the int8 kernels (retinanet/model/quantization.py)
+            key += (("int8", quantization.key),)
         if key not in self._engines:
             graph = prune_auxillary_head(self.graph) if serving else self.graph
             self._engines[key] = InferenceEngine(graph, self.variables, batch_size, self.device,
                                                  bn_epsilon=self.params.architecture.batch_norm.epsilon,
                                                  capture_graph=capture_graph,
                                                  f16=half_activations(self.params),
-                                                 launch_opts=self.launch_opts)
+                                                 launch_opts=self.launch_opts, quantization=quantization)
         return self._engines[key]
 
     def train_engine(self, batch_size, process_group=None, world_size=None, accumulation_steps=1):
@@ -244,7 +246,7 @@ class ModelBuilder:
                                           precision=params.floatx.precision)
         return model
 
-    def prepare_model_for_export(self, model, mode="tf"):
+    def prepare_model_for_export(self, model, mode="tf", quantization=None):
         model.optimizer = None
         skip_decoding = skip_nms = False
         if mode == "tf":
@@ -257,9 +259,11 @@ class ModelBuilder:
             skip_decoding = skip_nms = True
         else:
             raise ValueError("Invalid export model requested!")
-        return self.add_post_processing_stage(model, skip_decoding=skip_decoding, skip_nms=skip_nms)
+        return self.add_post_processing_stage(model, skip_decoding=skip_decoding, skip_nms=skip_nms,
+                                              quantization=quantization)
 
-    def add_post_processing_stage(self, model, skip_decoding=False, skip_nms=False, capture_graph=False):
+    def add_post_processing_stage(self, model, skip_decoding=False, skip_nms=False, capture_graph=False,
+                                  quantization=None):
         """model/builder.py:153-190: images -> {'boxes', 'scores', 'classes', 'valid_detections'}.
 
         The returned dict holds the stage's STATIC output buffers: the next call with the same batch size overwrites
@@ -284,7 +288,7 @@ class ModelBuilder:
 
         def inference_model(images, training=False):
             if not capture_graph:
-                eng = model.inference_engine(images.shape[0], serving=True)
+                eng = model.inference_engine(images.shape[0], serving=True, quantization=quantization)
                 return post(eng(images))
             # `serving_default` as ONE graph launch: the engine's launch list AND the post-processing stage's launches
             # (decode, compaction, per-class NMS, merge) are captured together — at batch 1 the step is ~75 short
@@ -294,7 +298,7 @@ class ModelBuilder:
             B = int(images.shape[0])
             st = graphs.get(B)
             if st is None:
-                eng = model.inference_engine(B, serving=True)
+                eng = model.inference_engine(B, serving=True, quantization=quantization)
                 if tuple(images.shape) != tuple(eng.t["images"].shape):
                     raise ValueError(f"expected images of shape {tuple(eng.t['images'].shape)}, got {tuple(images.shape)}")
                 post_b = DetectionPostProcess(params, anchors=anchors)

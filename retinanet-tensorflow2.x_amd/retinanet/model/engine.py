@@ -24,7 +24,7 @@ from .forward import pixel_pair_kernel, pixel_pair_ok  # noqa: F401  (host-side 
 
 class InferenceEngine:
     def __init__(self, graph, variables, batch_size, device, bn_epsilon=1e-3, capture_graph=False, f16=False,
-                 launch_opts=None):
+                 launch_opts=None, quantization=None):
         self.g = graph
         self.B = int(batch_size)
         self.dev = torch.device(device)
@@ -48,6 +48,12 @@ class InferenceEngine:
         self._capture = bool(capture_graph)
         with torch.cuda.device(self.dev):
             self._alloc()
+            # INT8 serving of the detection heads (retinanet/model/quantization.py): a QuantizationTable turns the
+            # class-head / box-head convs into rn_quantize_i8 + rn_conv3x3_i8_fwd launches; backbone and FPN stay as they are
+            self.int8 = None
+            if quantization is not None:
+                from .quantization import Int8Heads
+                self.int8 = Int8Heads(self, quantization)
             # split-K of the persistent conv kernels' last round: the launches of this engine run in order on one stream
             self.splitk_ws = _C.new_splitk_workspace(self.lib, self.dev, default_on=True)
             self.folded = FoldedConvs(self.lib, self.g, self.B, self.dev, self.h16, self.launch_opts, self.splitk_ws,
@@ -99,6 +105,8 @@ class InferenceEngine:
                 fc.load_se(variables, op)
             elif op["op"] == "dwconv":
                 fc.load_dw(variables, op)
+            elif op["op"] == "conv" and self.int8 is not None and op["out"] in self.int8.outs:
+                continue                                                              # int8 heads: packed below
             elif op["op"] in ("conv", "stem") and op["out"] not in self._bneck_skip:   # fused blocks: packed below
                 fc.load(variables, op)
             elif op["op"] == "topdown" and op.get("fusion"):
@@ -107,6 +115,8 @@ class InferenceEngine:
                     fc.stable(name, variables[name].to(self.dev, torch.float32).reshape(-1).clone())
         for fb in self.bneck.values():
             fb.load(variables, self.eps)
+        if self.int8 is not None:
+            self.int8.load(variables)
 
     # ---- launch list -------------------------------------------------------------------------
     def _side_launch(self, ops, second_of_split):
@@ -154,6 +164,25 @@ class InferenceEngine:
         self.step_io[name] = ({t for o in ops for t in (o["inp"], o.get("residual")) if t}, {o["out"] for o in ops})
         if side:
             self.side_steps.add(name)
+
+    def _add_step(self, fn, name, reads, writes, side=False):
+        self.steps.append((fn, name))
+        self.step_io[name] = (reads, writes)
+        if side:
+            self.side_steps.add(name)
+
+    def _add_int8_launches(self, ops):
+        """the grouped head launch `ops` on the int8 kernels: the quantiser in front of the first one, then one launch per
+        10 segments"""
+        q = self.int8
+        if not q.launches:
+            self._add_step(*q.quantize_step())
+        n = _C.RN_CONV_MAX_SEGMENTS
+        for j in range(0, len(ops), n):
+            sub = ops[j:j + n]
+            name = conv_launch_name("conv_i8:", sub, q.problems)
+            fn, reads, writes = q.conv_step(sub, name)
+            self._add_step(fn, name, reads, writes, side=self._side_launch(sub, j > 0))
 
     def _add_dw_launch(self, ops):
         p = dw_problem(self.g, ops, self.B, lambda o: self.t[o["inp"]], lambda o: self.t[o["out"]],
@@ -210,6 +239,11 @@ class InferenceEngine:
                 if fb is not None:                 # the block's first op in graph order carries the launch
                     self.steps.append((fb.launch, fb.name))
                     self.step_io[fb.name] = ({fb.blk["x"]}, {fb.blk["name"]})
+            elif kind == "conv" and self.int8 is not None and op["out"] in self.int8.outs:
+                grp = op.get("group") or op["out"]
+                if grp not in done_groups:
+                    done_groups.add(grp)
+                    self._add_int8_launches([o for o in self.g.ops if o["op"] == "conv" and (o.get("group") or o["out"]) == grp])
             elif kind == "conv":
                 grp = op.get("group")
                 if grp is None:
